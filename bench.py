@@ -2,12 +2,18 @@
 """Benchmark of the tagger hot path on MI355X (contract: see the task brief / DESIGN.md §Measurement).
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full          # + roofline, per-kernel table, sustained leg, other configs, CPU baseline
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One "step" = forward + backward + Adam(eps 1e-7) of the restricted-window transformer tagger (BASELINE.json
 configs[1]: d=1792 early-fused embeddings, 8 heads, ff=256, one-sided window 15, 1 layer, focal loss, bf16) on one
 synthetic batch of 64 documents x 256 sentences per GPU, inputs resident in HBM.  Weak scaling: every rank gets its
 own 64 documents; gradients are all-reduced over RCCL.  Rank 0 prints ONE JSON line.
+
+A plain run does only what its headline needs: set up, --warmup steps, --steps timed steps, the JSON line (`ms_per_step` = one timed
+step).  Everything else it can measure (HIP-event brackets for `roofline` / `kernels`, the sustained leg under `extra`, the other
+BASELINE configurations, the host-batch legs, `cpu_baseline`) runs only with --full.
 """
 import argparse
 import json
@@ -67,6 +73,25 @@ def csrc_sha():
             h.update(fn.encode())
             h.update(open(os.path.join(d, fn), 'rb').read())
     return h.hexdigest()[:16]
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_SAMPLE_CAP = 1 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write each tensor as `path/<name>.npy` in float32, at most DUMP_BUDGET_BYTES in all.  A tensor with more than
+    `cap` elements is replaced by a fixed sample of them: its flattened elements at `unique(randint(numel, (cap,)))` drawn from a generator
+    seeded with 0 (1-D, sorted), so that two builds sample the same positions."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    cap = min(DUMP_SAMPLE_CAP, (DUMP_BUDGET_BYTES - 4096 * len(arrays)) // (4 * len(arrays)))    # 4096: room for each .npy header
+    for name, t in arrays.items():
+        a = t.detach().float().cpu()
+        if a.numel() > cap:
+            idx = torch.randint(a.numel(), (cap,), generator=torch.Generator().manual_seed(0)).unique()
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + '.npy'), a.numpy())
 
 
 def cpu_baseline(args, D, ff, heads, window, n_layers):
@@ -308,7 +333,12 @@ def main():
     ap.add_argument('--layers', type=int, default=None)
     ap.add_argument('--dtype', default='bf16', choices=['bf16', 'fp32'])
     ap.add_argument('--cpu-docs', type=int, default=32)
-    ap.add_argument('--sustained-steps', type=int, default=1000, help='extra timed leg after the K-step region (0 = skip); reported under "extra"')
+    ap.add_argument('--full', action='store_true', help='also measure what the headline does not need: HIP-event brackets (roofline, kernels), '
+                    'the sustained leg, the other BASELINE configurations and host-batch legs, the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps, write the loss and the parameters of the '
+                    'last timed step as DIR/<name>.npy (float32, at most 64 MB; larger tensors as a fixed seeded sample)')
+    ap.add_argument('--sustained-steps', type=int, default=None, help='extra timed leg after the K-step region (0 = skip; default 1000 with '
+                    '--full, else 0); reported under "extra"')
     ap.add_argument('--h2d', default=None, choices=['pinned', 'pageable', 'collater'], help='variant line: host batches through prefetch.DevicePrefetcher '
                     'in the loop (PCIe-inclusive step); the batches live in pinned or pageable host memory')
     ap.add_argument('--h2d-wire', default='fp32', choices=['fp32', 'bf16'], help='--h2d: dtype of the embeddings on the wire')
@@ -322,6 +352,10 @@ def main():
                     'typical use: --infer --docs 1 --seq 2437 (the longest RadioNews document)')
     ap.add_argument('--no-pack', action='store_true', help='with --ragged: keep the padded rows in the encoder (A/B of the packed training path)')
     args = ap.parse_args()
+    if args.dump_outputs and (args.infer or args.h2d):
+        ap.error('--dump-outputs writes the outputs of the training step: not with --infer or --h2d')
+    if args.sustained_steps is None:
+        args.sustained_steps = 1000 if args.full else 0
 
     import torch.distributed as dist
     # MTS_BENCH_REHEARSAL=1: every rank on cuda:0 over gloo -- exercises the N>1 code path (sharding, gradient-ready hooks,
@@ -431,10 +465,11 @@ def main():
                                                      f'{args.docs} docs x {args.seq} sentences per GPU'}, 'h2d': leg}))
         return
 
-    # Warm-up with every GEMM / band-attention launch bracketed by HIP events: finds the dominant kernel symbol and fills the
+    # --full: warm-up with every GEMM / band-attention launch bracketed by HIP events: finds the dominant kernel symbol and fills the
     # per-kernel table.  An event pair costs a few microseconds of stream time (14 timed launches = ~5 % of this step), so the
     # timed region itself brackets only the launches of that dominant symbol (+ the band-attention forward, the HBM headline).
-    wtimer = None if args.no_kernel_timer else ops.KernelTimer()
+    kernel_timer = args.full and not args.no_kernel_timer
+    wtimer = ops.KernelTimer() if kernel_timer else None
     for i in range(args.warmup):
         ops.TIMER = wtimer if i > 0 else None        # the very first step only primes caches (which kernel the cost model picks per shape)
         trainer.step(batch)
@@ -447,7 +482,7 @@ def main():
             wsym[(tag[1], tag[7])] = wsym.get((tag[1], tag[7]), 0.0) + ms
     dom_key = max(wsym.items(), key=lambda kv: kv[1])[0] if wsym else None
     # (fewer than two warm-up steps: nothing was measured yet, so bracket everything as before)
-    timer = None if args.no_kernel_timer else ops.KernelTimer(
+    timer = None if not kernel_timer else ops.KernelTimer(
         only=(lambda tag: tag[0] == 'gemm' and (tag[1], tag[7]) == dom_key) if dom_key is not None else None)
     # ... and only in every `--timer-every`-th step of the region (default 5): measured on MI355X, three bracketed launches per step cost
     # 0.08-0.16 ms of a 1.95 ms step (each event is a timestamp packet behind a queue barrier) -- 2.05 ms with every step bracketed against
@@ -471,6 +506,8 @@ def main():
         t = torch.tensor([elapsed], device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'loss': loss, **model.state_dict()})
     # sustained figure: the K-step value above is taken on a chip that has been busy for a fraction of a second; under sustained
     # load the clock settles lower (DVFS), so the same build is timed again over >= 1000 steps (no per-kernel events)
     sustained = None
@@ -570,12 +607,12 @@ def main():
                 out['kernels']['band_attn_fwd'] = {**other['band_fwd'], 'algorithmic_GBps': gbs, 'hbm_frac': gbs / HBM_PEAK_GBS}
             if 'band_bwd' in wother:
                 out['kernels']['band_attn_bwd (one pass)'] = wother['band_bwd']
-        if world == 1 and not single_rank_dp and not args.no_other_configs and cfg_label == 'BASELINE configs[1]':
+        if args.full and world == 1 and not single_rank_dp and not args.no_other_configs and cfg_label == 'BASELINE configs[1]':
             out.setdefault('extra', {})['other_configs'] = other_configs(device)
-        if world == 1 and not single_rank_dp and not args.no_other_configs and cfg_label == 'BASELINE configs[1]':
+        if args.full and world == 1 and not single_rank_dp and not args.no_other_configs and cfg_label == 'BASELINE configs[1]':
             out['extra']['h2d'] = {f'{src}, {w} on the wire': h2d_leg(trainer, args.docs, args.seq, D, D2, device, 60, 15, w, src)
                                    for src, w in (('pinned', 'fp32'), ('pageable', 'fp32'), ('pinned', 'bf16'), ('collater', 'fp32'), ('collater', 'bf16'))}
-        if world == 1 and not args.no_cpu_baseline and args.arch == 'transformer':
+        if args.full and world == 1 and not args.no_cpu_baseline and args.arch == 'transformer':
             out['cpu_baseline'] = cpu_baseline(args, D, ff, heads, window, n_layers)
         print(json.dumps(out))
     if world > 1 or single_rank_dp:

@@ -1,4 +1,5 @@
-"""bench.py contract (driver-facing): one JSON line with the agreed keys, roofline and cpu_baseline objects, on a tiny run."""
+"""bench.py contract (driver-facing): one JSON line with the agreed keys; with --full also the roofline and cpu_baseline objects, on a
+tiny run."""
 import json
 import os
 import subprocess
@@ -19,7 +20,7 @@ def _run(*flags):
 
 
 def test_bench_json_contract_transformer():
-    j = _run('--steps', '3', '--warmup', '2', '--docs', '8', '--seq', '128', '--cpu-docs', '1')
+    j = _run('--full', '--steps', '3', '--warmup', '2', '--docs', '8', '--seq', '128', '--cpu-docs', '1')
     for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline', 'dtype',
               'data', 'config', 'roofline', 'cpu_baseline'):
         assert k in j, k
@@ -36,6 +37,28 @@ def test_bench_json_contract_transformer():
     assert c['kind'] in ('port', 'reference') and c['cores'] >= 1 and c['value'] > 0 and c['unit'] == 'sentences/s' and 'sample' in c
 
 
+def test_plain_line_is_lean_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and carries none of the --full measurements.  --dump-outputs writes the loss
+    and the parameters after the last timed step (float32, at most 64 MB), bit for bit the same in a second run with the same arguments."""
+    import numpy as np
+    flags = ('--steps', '3', '--warmup', '2', '--docs', '8', '--seq', '128')
+    a = _run(*flags, '--dump-outputs', str(tmp_path / 'a'))
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert k in a, k
+    assert a['steps'] == 3 and a['warmup'] == 2 and a['unit'] == 'sentences/s' and a['dtype'] == 'bf16' and a['higher_is_better'] is True
+    assert abs(a['value'] - 8 * 128 * 1000.0 / a['ms_per_step']) < 1e-3 * a['value']
+    assert not {'roofline', 'kernels', 'cpu_baseline', 'extra'} & set(a), sorted(a)
+    b = _run(*flags, '--dump-outputs', str(tmp_path / 'b'))
+    names = sorted(os.listdir(tmp_path / 'a'))
+    assert 'loss.npy' in names and len(names) > 2 and names == sorted(os.listdir(tmp_path / 'b'))
+    assert sum(os.path.getsize(tmp_path / 'a' / n) for n in names) <= 64 << 20
+    assert float(np.load(tmp_path / 'a' / 'loss.npy')) == a['final_loss']
+    for n in names:
+        x, y = np.load(tmp_path / 'a' / n), np.load(tmp_path / 'b' / n)
+        assert x.dtype == np.float32 and np.isfinite(x).all(), n
+        np.testing.assert_array_equal(x, y, err_msg=n)
+
+
 @pytest.mark.parametrize('arch', ['bilstm', 'bilstm_crf', 'latefusion'])
 def test_bench_runs_other_architectures(arch):
     j = _run('--arch', arch, '--steps', '2', '--warmup', '1', '--docs', '16', '--seq', '64', '--no-cpu-baseline')
@@ -49,9 +72,9 @@ def test_bench_ragged_counts_valid_sentences_only():
 
 
 def test_default_line_witnesses_the_other_baseline_configurations():
-    """the driver's BENCH record carries 50-step figures of configs[2] (focal and CRF heads), configs[4]'s per-GPU
+    """the --full line carries 50-step figures of configs[2] (focal and CRF heads), configs[4]'s per-GPU
     workload and the fp32 parity mode (transformer and BiLSTM) under extra.other_configs; `value` / `roofline` stay on configs[1]."""
-    j = _run('--steps', '3', '--warmup', '2', '--cpu-docs', '1', '--sustained-steps', '0')
+    j = _run('--full', '--steps', '3', '--warmup', '2', '--cpu-docs', '1', '--sustained-steps', '0')
     assert j['config']['workload'].startswith('BASELINE configs[1]')
     oc = j['extra']['other_configs']
     assert len(oc) == 5 and sum('configs[2]' in k for k in oc) == 3 and sum('configs[4]' in k for k in oc) == 1 and sum('fp32' in k for k in oc) == 2

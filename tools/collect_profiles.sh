@@ -8,9 +8,9 @@ TAG=${1:-r03}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-B="--no-cpu-baseline --no-other-configs"
+B="--full --no-cpu-baseline --no-other-configs"
 echo "[1] default bench line (with cpu_baseline and sustained leg)"
-python3 bench.py > $OUT/bench.json 2> $OUT/bench.err || exit 1
+python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err || exit 1
 echo "[2] kernel trace + stats of the same command (no cpu baseline)"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o tr -- python3 bench.py $B --sustained-steps 0 > $OUT/bench_profiled.json 2> $OUT/trace.err || exit 1
 echo "[3] HBM-side traffic: FETCH_SIZE and WRITE_SIZE in separate passes"
