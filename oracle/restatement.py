@@ -232,7 +232,8 @@ def late_fusion_scores(x1: Tensor, x2: Tensor, lengths: Tensor, p: Dict[str, Ten
 # --------------------------------------------------------------------------------------------
 # restricted-window self-attention encoder (live path = HF LongformerModel, local attention only)
 # --------------------------------------------------------------------------------------------
-def band_attention(q: Tensor, k: Tensor, v: Tensor, lengths: Tensor, radius: int) -> Tensor:
+def band_attention(q: Tensor, k: Tensor, v: Tensor, lengths: Tensor, radius: int, return_probs: bool = False,
+                   keep: Optional[Tensor] = None):
     """Per-query softmax over keys j in [i-radius, i+radius] ∩ [0, len_b).
 
     q,k,v: [B, L, heads, hd]; q already scaled by 1/sqrt(hd) (HF:514).
@@ -240,6 +241,10 @@ def band_attention(q: Tensor, k: Tensor, v: Tensor, lengths: Tensor, radius: int
     padded keys get finfo.min added (HF:524-536) => probability exactly 0; rows of masked queries
     are zeroed (HF:579).  The legacy implementation models/RestrictedTransformerLayer.py:509-636
     computes the same window softmax position by position (without the padding mask).
+
+    keep (optional, [B, L, heads, 2*radius+1]): attention dropout (HF:590) -- multiplies the probabilities before they weight V
+    (pass the keep mask times 1/(1-p)).  return_probs: also return the probabilities [B, L, heads, 2*radius+1] (slot c <-> key
+    i - radius + c), before ``keep``.
     """
     B, L, Hh, hd = q.shape
     W = 2 * radius + 1
@@ -269,10 +274,11 @@ def band_attention(q: Tensor, k: Tensor, v: Tensor, lengths: Tensor, radius: int
     s = torch.where(q_ok.view(B, L, 1, 1), s, torch.zeros_like(s))
     pr = torch.softmax(s, dim=-1)
     pr = pr * q_ok.view(B, L, 1, 1).to(pr.dtype)
+    pv = pr if keep is None else pr * keep.to(pr.dtype)
     out = torch.zeros_like(q)
     for c in range(W):
-        out = out + pr[..., c].unsqueeze(-1) * shifted(v, c - radius)
-    return out
+        out = out + pv[..., c].unsqueeze(-1) * shifted(v, c - radius)
+    return (out, pr) if return_probs else out
 
 
 def band_attention_blocked(q: Tensor, k: Tensor, v: Tensor, lengths: Tensor, radius: int, block: int = 64) -> Tensor:

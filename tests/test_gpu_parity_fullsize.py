@@ -258,7 +258,7 @@ def test_late_fusion_64x512_bf16_against_the_oracle():
 
 
 # ------------------------------------------------------------------------------------------------ fp32 parity mode: bit-exact boundary lists
-@pytest.mark.parametrize('arch', ['transformer', 'bilstm', 'bilstm_crf'])
+@pytest.mark.parametrize('arch', ['transformer', 'transformer_w120', 'bilstm', 'bilstm_crf'])
 def test_fp32_parity_mode_64x256x1792_boundary_lists_are_bit_exact(arch):
     """north_star: "outputs match the reference CPU path ... (bit-exact boundary indices under greedy decode)".  The drop-in classes' default
     arithmetic (fp32) at the BASELINE shape against the fp64 oracle on the same fp32 weights and inputs: scores 5e-5 abs, loss 1e-5 rel, and
@@ -271,6 +271,12 @@ def test_fp32_parity_mode_64x256x1792_boundary_lists_are_bit_exact(arch):
     if arch == 'transformer':
         m = Transformer_segmenter(2, D, 256, num_layers=1, nheads=8, loss_fn='FocalLoss', window_size=30, compute_dtype='fp32',
                                   max_position_embedding=Lq + 2, seed=51).to(DEV)
+    elif arch == 'transformer_w120':
+        # the drop-in class as users build it: TextSegmenter's default attention_window 120 (radius 60: the generic fp32 kernels)
+        from multimodaltopicsegmentation_amd import TextSegmenter
+        torch.manual_seed(51)
+        m = TextSegmenter(2, D, 256, architecture='Transformer', nheads=8, loss_fn='FocalLoss', compute_dtype='fp32').to(DEV).model
+        assert m.radii == [60]
     elif arch == 'bilstm':
         m = BiLSTM(2, D, 256, num_layers=2, loss_fn='FocalLoss', compute_dtype='fp32', seed=51).to(DEV)
     else:
@@ -281,8 +287,9 @@ def test_fp32_parity_mode_64x256x1792_boundary_lists_are_bit_exact(arch):
     torch.set_num_threads(min(16, torch.get_num_threads()))
     p = {k: v.detach().cpu().double() for k, v in m.state_dict().items()}
     with torch.no_grad():
-        if arch == 'transformer':
-            ref = R.transformer_scores(x.double(), lengths, p, 8, R.pyramidal_radii(1, 30), attention=R.band_attention_blocked)
+        if arch in ('transformer', 'transformer_w120'):
+            radii = R.pyramidal_radii(1, 120 if arch == 'transformer_w120' else 30)
+            ref = R.transformer_scores(x.double(), lengths, p, 8, radii, attention=R.band_attention_blocked)
             ref_loss = R.tagger_loss(ref, lengths, y.double(), 'FocalLoss')
         elif arch == 'bilstm':
             ref = R.bilstm_scores(x.double(), lengths, p, 2, batched=True)
@@ -329,6 +336,77 @@ def test_transformer_64x256x1792_ragged_packed_bf16_against_the_oracle():
     worst = _compare_grads(m, p, exact_zero={kb: 'model.model.encoder.layer.0.attention.self.query.bias'})
     flips = _check_greedy_lists(m, (x.to(DEV),), lengths, ref_scores, exact=False)
     print('transformer ragged/packed worst:', max(v[0] for v in worst.values()), max(v[1] for v in worst.values()), 'flips', flips)
+
+
+def _band_radii_that_ran(run):
+    """run() under a KernelTimer: the radii of the band-attention forward and backward launches (('band_fwd', B, L, D, heads, radius))"""
+    from multimodaltopicsegmentation_amd import ops
+    timer = ops.KernelTimer()
+    ops.TIMER = timer
+    try:
+        out = run()
+    finally:
+        ops.TIMER = None
+    torch.cuda.synchronize()
+    ran = timer.summary()
+    return out, {t[5] for t in ran if t[0] == 'band_fwd'}, {t[5] for t in ran if t[0] == 'band_bwd'}
+
+
+def _transformer_bf16_against_the_oracle(m, radii, x, y, lengths, packed):
+    """loss_and_grad of a bf16 Transformer_segmenter (weights and inputs bf16-exact) against the fp64 oracle at every radius: loss, scores,
+    every gradient (key.bias of every layer: exactly 0), greedy lists inside DECODE_MARGIN"""
+    from oracle import restatement as R
+    B, Lq, _ = x.shape
+    n_valid = int(lengths.sum())
+    (loss, scores), fwd_radii, bwd_radii = _band_radii_that_ran(lambda: m.loss_and_grad(x.to(DEV), lengths, y.to(DEV), True))
+    assert m.radii == list(radii) and fwd_radii == set(radii) and bwd_radii == set(radii), (m.radii, fwd_radii, bwd_radii)
+    if packed:
+        assert n_valid < 0.9 * B * Lq
+        assert tuple(scores.shape) == (n_valid, 1), scores.shape      # pack_rows = 'auto' packed the batch
+    torch.set_num_threads(min(16, torch.get_num_threads()))
+    p = _oracle_params(m, torch.float64)
+    ref_scores = R.transformer_scores(x.double(), lengths, p, m.nheads, radii, attention=R.band_attention_blocked)
+    ref_loss = R.tagger_loss(ref_scores, lengths, y.double(), 'FocalLoss')
+    ref_loss.backward()
+    assert abs(float(loss) - float(ref_loss)) <= 2e-3 * abs(float(ref_loss)), (float(loss), float(ref_loss))
+    valid = R.create_mask(Lq, lengths)
+    d = (scores.detach().cpu().double().view(-1) - ref_scores.detach()[valid].view(-1)).abs()      # packed: valid rows document after document
+    assert float(d.max()) <= 3e-2 and float(d.mean()) <= 3e-3, (float(d.max()), float(d.mean()))
+    # key.bias: the softmax over a window is invariant to a shift common to all its keys -- in every layer
+    lay = 'model.model.encoder.layer.{}.attention.self.'
+    worst = _compare_grads(m, p, exact_zero={lay.format(li) + 'key.bias': lay.format(li) + 'query.bias' for li in range(len(radii))})
+    flips = _check_greedy_lists(m, (x.to(DEV),), lengths, ref_scores, exact=False)
+    return worst, flips
+
+
+@pytest.mark.parametrize('batch', ['equal', 'ragged'])
+def test_transformer_2layer_pyramidal_64x256x1792_bf16_against_the_oracle(batch):
+    """-nl 2 at window 30 (models/CRF.py:529): layer 0 at radius 30 (MFMA 6 key blocks, two-kernel backward), layer 1 at radius 15 (4 key
+    blocks, one-pass backward), both at head dim 224, equal lengths and ragged (packed rows)"""
+    from oracle import restatement as R
+    from multimodaltopicsegmentation_amd.taggers import Transformer_segmenter
+    B, Lq, D, FF, HEADS = 64, 256, 1792, 256, 8
+    m = _round_to_bf16_(Transformer_segmenter(2, D, FF, num_layers=2, nheads=HEADS, loss_fn='FocalLoss', window_size=30,
+                                               compute_dtype='bf16', max_position_embedding=Lq + 2, seed=91).to(DEV))
+    x, _, y, lengths = _full_batch(B, Lq, D, 92) if batch == 'equal' else _ragged_batch(B, Lq, D, 93)
+    worst, flips = _transformer_bf16_against_the_oracle(m, R.pyramidal_radii(2, 30), x, y, lengths, packed=batch == 'ragged')
+    print(f'transformer 2-layer ({batch}) worst (max-ratio, l2-ratio):', max(v[0] for v in worst.values()), max(v[1] for v in worst.values()),
+          'flips', flips)
+
+
+def test_transformer_default_window_64x256x1792_bf16_against_the_oracle():
+    """The drop-in class as users build it: TextSegmenter without attention_window -> window 120, radius 60 (MFMA 10 key blocks at head dim
+    224), ragged documents on the packed path"""
+    from oracle import restatement as R
+    from multimodaltopicsegmentation_amd import TextSegmenter
+    B, Lq, D = 64, 256, 1792
+    torch.manual_seed(95)
+    m = _round_to_bf16_(TextSegmenter(2, D, 256, architecture='Transformer', nheads=8, loss_fn='FocalLoss', compute_dtype='bf16').to(DEV).model)
+    assert m.radii == [60]
+    x, _, y, lengths = _ragged_batch(B, Lq, D, 96)
+    worst, flips = _transformer_bf16_against_the_oracle(m, R.pyramidal_radii(1, 120), x, y, lengths, packed=True)
+    print('transformer default window (radius 60) worst (max-ratio, l2-ratio):', max(v[0] for v in worst.values()),
+          max(v[1] for v in worst.values()), 'flips', flips)
 
 
 @pytest.mark.parametrize('head', ['focal', 'crf'])

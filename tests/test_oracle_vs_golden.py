@@ -249,7 +249,9 @@ def test_blocked_band_attention_equals_the_shifted_statement():
     """bench.py's cpu_baseline uses the block-wise matmul form; it must be the same function (values and gradients), ragged
     lengths, a document shorter than the radius, L not a multiple of the block."""
     g = torch.Generator().manual_seed(0)
-    for (B, L, Hh, hd, w, block) in ((3, 50, 2, 8, 15, 16), (2, 130, 1, 4, 4, 64), (2, 7, 2, 4, 15, 64)):
+    # the last two: radius >= block (the TextSegmenter default window 120 and layer 0 of a 2-layer pyramid at window 120)
+    for (B, L, Hh, hd, w, block) in ((3, 50, 2, 8, 15, 16), (2, 130, 1, 4, 4, 64), (2, 7, 2, 4, 15, 64), (3, 200, 2, 4, 60, 64),
+                                     (2, 300, 1, 4, 120, 64)):
         lengths = torch.randint(1, L + 1, (B,), generator=g)
         lengths[0] = L
         q, k, v = (torch.randn(B, L, Hh, hd, generator=g, dtype=torch.float64).requires_grad_(True) for _ in range(3))
@@ -268,3 +270,39 @@ def test_blocked_band_attention_equals_the_shifted_statement():
     sc = R.transformer_scores(_t(gg['x']), torch.from_numpy(gg['lengths']), p, heads, R.pyramidal_radii(NL, window),
                               attention=R.band_attention_blocked)
     np.testing.assert_allclose(sc.numpy(), gg['scores'], atol=2e-5, rtol=0)
+
+
+def test_band_attention_probs_and_keep_options():
+    """return_probs / keep (the kernel tests' slot-by-slot and dropout oracle) restate the same function: the probabilities weighted
+    by the shifted values give ctx, an all-ones keep changes nothing, a keep mask acts on the probabilities that weight V only."""
+    g = torch.Generator().manual_seed(1)
+    B, L, Hh, hd, w = 3, 40, 2, 4, 7
+    W = 2 * w + 1
+    lengths = torch.tensor([40, 9, 1])
+    q, k, v = (torch.randn(B, L, Hh, hd, generator=g, dtype=torch.float64) for _ in range(3))
+    base = R.band_attention(q, k, v, lengths, w)
+    out, pr = R.band_attention(q, k, v, lengths, w, return_probs=True)
+    assert torch.equal(out, base)
+    assert pr.shape == (B, L, Hh, W)
+    ones = R.band_attention(q, k, v, lengths, w, keep=torch.ones(B, L, Hh, W, dtype=torch.float64))
+    assert torch.equal(ones, base)
+    # slot c <-> key j = i - w + c: probabilities times the keys' values, summed, are ctx; keys outside [0, len_b) and masked
+    # queries carry probability exactly 0
+    i = torch.arange(L).view(L, 1)
+    j = i - w + torch.arange(W).view(1, W)                                   # [L, W]
+    jc = j.clamp(0, L - 1)
+    vg = v[:, jc]                                                            # [B, L, W, Hh, hd]
+    assert float((torch.einsum('blhc,blchd->blhd', pr, vg) - base).abs().max()) < 1e-12
+    for b, n in enumerate(lengths.tolist()):
+        outside = (j < 0) | (j >= n)
+        assert float(pr[b].permute(0, 2, 1)[outside].abs().max()) == 0.0
+        assert n == L or float(pr[b, n:].abs().max()) == 0.0
+        assert float((pr[b, :n].sum(-1) - 1).abs().max()) < 1e-12
+    keep = (torch.rand(B, L, Hh, W, generator=g) >= 0.3).double() / 0.7
+    qq, kk, vv = (t.clone().requires_grad_(True) for t in (q, k, v))
+    dropped, pr2 = R.band_attention(qq, kk, vv, lengths, w, return_probs=True, keep=keep)
+    assert torch.equal(pr2, pr)                                              # the returned probabilities are the undropped ones
+    assert float((torch.einsum('blhc,blchd->blhd', pr * keep, vg) - dropped).abs().max()) < 1e-12
+    assert float((dropped - base).abs().max()) > 1e-2
+    dropped.sum().backward()
+    assert all(t.grad is not None and torch.isfinite(t.grad).all() for t in (qq, kk, vv))
