@@ -74,6 +74,7 @@ const char* mts_version(void);
  * of the 128x128 kernel accumulates in place) ; "gemm_deep" = 1 (four-buffer copy pipeline of the 128x128 kernel for grids of at
  * most one workgroup per CU) | 0 ; "band_mfma" = 1 | 0 ; "band_fused_bwd" = 1 (bf16 band attention backward in one pass where it applies:
  * radius <= 15, head dim <= 224) | 0 (two kernels) ; "lstm_parts" = 4 (CU-quad recurrences at H = 256, bf16 and fp32) | 2 (CU pair, bf16) ;
+ * "full_mfma" = 1 | 0 (bf16 full attention on the matrix-core kernels where head dim % 32 == 0 and <= 256, else generic) ;
  * "lstm_pair_spin_limit" = re-polls before a CU-pair LSTM workgroup gives
  * up on its partner (-1 = default 2^22; tests use 0) ; "lstm_pair_max_pairs" = CU pairs per recurrence launch (1..64, default 64) */
 int mts_set_option(const char* key, int value);
@@ -273,6 +274,35 @@ int mts_band_attn_bwd(void* stream, int dtype, int B, int L, int D, int heads, i
                       const void* qkv, const int32_t* lengths, const float* probs, const void* dctx,
                       void* dqkv, float* dscores, float* dbias, void* workspace, const int32_t* row0, int n_rows,
                       float drop_p, uint64_t drop_seed);
+
+/* ---------------------------------------------------------------------------------------------
+ * Full self-attention (every valid key of the document).
+ * Replaces: BertSelfAttention of the BertModel inside Classic_Transformer (models/RestrictedTransformerLayer.py:16-63, used by
+ * Transformer_segmenter(restricted=False), models/CRF.py:543-549); plus the backward.
+ * Operands as for the band kernels: qkv [rows, 3D] act dtype with q already scaled, lengths int32 [B] (NULL = all L; every
+ * lengths[b] >= 1), row0 (optional) = packed rows, ctx [rows, D].  Query i of document b attends to keys j < len_b: padded keys get
+ * probability exactly 0 (their tiles are never visited); padded query rows of the [B, L] layout are NOT zeroed -- they attend to the
+ * document's valid keys like any other row (BERT has no masked-row step).
+ * lse: fp32 [rows, heads] = log sum_j exp(s_ij), saved by the forward; the backward recomputes P = exp(S - lse) from q, k and lse,
+ * and takes delta = rowsum(dCtx o ctx) from the saved ctx.  Nothing [L, L] is ever stored.
+ * drop_p > 0: dropout on the attention probabilities (BERT's attention_probs_dropout_prob): what multiplies V is
+ * keep ? p / (1 - drop_p) : 0 with
+ *     keep = mts_hash32(drop_seed, ((uint64_t)grow * heads + h) * L + j) >= (uint32_t)max(1, min(2^32 - 1, drop_p * 2^32))
+ * grow = the activation row of the query (packed or not), L = the batch's padded length, j = the key's position in its document
+ * (mts_hash32: csrc/common.h, splitmix64 finaliser, high 32 bits).  The backward, given the same drop_p / drop_seed, regenerates it.
+ * Head dims: multiples of 4 (fp32) / 8 (bf16) up to 512 whose staged tiles fit 160 KiB of LDS (fp32: up to 292; bf16: up to 512);
+ * anything else is MTS_ERR_UNSUPPORTED before any launch.  bf16 with head dim % 32 == 0 and <= 256 runs on matrix-core kernels
+ * (v_mfma_f32_16x16x32_bf16); mts_set_option("full_mfma", 0) sends it to the generic kernels, which serve every other shape.
+ * mts_full_attn_bwd: dqkv [rows, 3D] (dq multiplied by q_scale); dbias (optional) fp32 [3D] = column sums of dqkv;
+ * workspace (REQUIRED) of mts_full_attn_bwd_workspace(B, L, D, heads) bytes.  Two kernels (dQ per query tile, dK/dV per key tile),
+ * no atomics: bitwise reproducible.
+ * ------------------------------------------------------------------------------------------- */
+int mts_full_attn_fwd(void* stream, int dtype, int B, int L, int D, int heads, const void* qkv, const int32_t* lengths,
+                      void* ctx, float* lse, const int32_t* row0, float drop_p, uint64_t drop_seed);
+size_t mts_full_attn_bwd_workspace(int B, int L, int D, int heads);
+int mts_full_attn_bwd(void* stream, int dtype, int B, int L, int D, int heads, float q_scale, const void* qkv,
+                      const int32_t* lengths, const float* lse, const void* ctx, const void* dctx, void* dqkv, float* dbias,
+                      void* workspace, const int32_t* row0, int n_rows, float drop_p, uint64_t drop_seed);
 
 /* ---------------------------------------------------------------------------------------------
  * Tagger head tail: loss + its gradient, and greedy decode.

@@ -50,7 +50,7 @@ class TextSegmenter(_Base):
                  architecture='biLSTMCRF', lr=0.01, dropout_in=0.0, dropout_out=0.0, optimizer='SGD', positional_encoding=True,
                  nheads=8, end_boundary=False, threshold=None, search_threshold=False, metric='Pk', cosine_loss=False,
                  zero_baseline=False, loss_fn='CrossEntropy', no_validation=False, all_results=False, all_scores=False, alpha=0.9,
-                 gamma=2, attention_window=120, switch='dense', compute_dtype=None, ksplit=False):
+                 gamma=2, attention_window=120, switch='dense', compute_dtype=None, ksplit=False, restricted=True):
         super().__init__()
         self.validation = not no_validation
         # ksplit=True (extension, default off): an early-fusion model takes the batch's two embedding tensors ('src_tokens' = text,
@@ -58,6 +58,8 @@ class TextSegmenter(_Base):
         # host-side concat of utils/load_datasets_precomputed.py:158-161 ever being made (datasets.load_dataset_from_precomputed(
         # ..., split_modalities=True) keeps the two directories apart)
         self.ksplit = bool(ksplit)
+        # restricted (extension, default True): False makes architecture='Transformer' build the reference's full-attention encoder
+        # (Transformer_segmenter(restricted=False) = a BertModel, models/CRF.py:543-549) instead of the restricted-window one
         self.cos = cosine_loss
         self.double_input = False
         self.domain = False
@@ -75,7 +77,8 @@ class TextSegmenter(_Base):
             self.model = Transformer_segmenter(tagset_size, embedding_dim, hidden_dim, num_layers=num_layers, dropout_in=dropout_in,
                                                dropout_out=dropout_out, batch_first=batch_first, loss_fn=loss_fn,
                                                positional_encoding=positional_encoding, nheads=nheads, threshold=threshold,
-                                               alpha=alpha, gamma=gamma, window_size=attention_window, compute_dtype=compute_dtype)
+                                               alpha=alpha, gamma=gamma, window_size=attention_window, compute_dtype=compute_dtype,
+                                               restricted=restricted)
         elif architecture == 'BiLSTMLateFusion':
             self.model = BiLSTMLateFusion(tagset_size, embedding_dim, hidden_dim, num_layers=num_layers, bidirectional=bidirectional,
                                           dropout_in=dropout_in, dropout_out=dropout_out, batch_first=batch_first, LSTM=LSTM,

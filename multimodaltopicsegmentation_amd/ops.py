@@ -323,6 +323,24 @@ def band_attn_bwd(qkv, lengths, probs, dctx, B, Lq, D, heads, radius, dqkv, dsco
                                     qkv.shape[0] if row0 is not None else 0, float(drop_p), int(drop_seed)))
 
 
+def full_attn_fwd(qkv, lengths, B, Lq, D, heads, ctx, lse, row0=None, drop_p=0.0, drop_seed=0):
+    """Full self-attention over every valid key of each document; lse (fp32 [rows, heads]) receives the per-row log-sum-exp.
+    row0 (int32 [B], optional): packed batch, as for band_attn_fwd."""
+    with _timed(('full_fwd', B, Lq, D, heads)):
+        check(lib.mts_full_attn_fwd(stream_ptr(), dtype_code(qkv.dtype), B, Lq, D, heads, ptr(qkv), ptr(lengths), ptr(ctx), ptr(lse),
+                                    ptr(row0), float(drop_p), int(drop_seed)))
+
+
+def full_attn_bwd(qkv, lengths, lse, ctx, dctx, B, Lq, D, heads, dqkv, dbias=None, row0=None, drop_p=0.0, drop_seed=0):
+    """Backward of full_attn_fwd from its saved ctx and lse; dbias (fp32 [3D], optional): column sums of dqkv."""
+    q_scale = 1.0 / math.sqrt(D // heads)
+    ws = _scratch(lib.mts_full_attn_bwd_workspace(B, Lq, D, heads), qkv.device, 'full_bwd')
+    with _timed(('full_bwd', B, Lq, D, heads)):
+        check(lib.mts_full_attn_bwd(stream_ptr(), dtype_code(qkv.dtype), B, Lq, D, heads, q_scale, ptr(qkv), ptr(lengths), ptr(lse),
+                                    ptr(ctx), ptr(dctx), ptr(dqkv), ptr(dbias), ptr(ws), ptr(row0),
+                                    qkv.shape[0] if row0 is not None else 0, float(drop_p), int(drop_seed)))
+
+
 def tagger_loss(kind, scores, targets, lengths, alpha, gamma, loss_out, dscores, row_src=None, batch_shape=None):
     """scores [B, L, n_out]; or, for a packed batch, [n_rows, n_out] with row_src (int32 [n_rows]) and batch_shape = (B, L)."""
     if row_src is None:

@@ -231,14 +231,18 @@ class _TaggerBase(FlatModule):
         D, F, H = self.embedding_dim, self._ffp, self.nheads
         ws = self._ws
         wf, pf = self._weights(), self._flat
-        slots = ops.band_slots(radius)
+        slots = ops.band_slots(radius) if radius is not None else 0
         qkv = ws.get(f'qkv{tag}', N, 3 * D, dt, dev)
         ops.linear_fwd(h, self._lt(wf, names, 'wqkv', 3 * D, D), self._lt(pf, names, 'bqkv', 1, 3 * D).view(-1), qkv,
                        colscale=1.0 / math.sqrt(D // H), ncols_scaled=D)
         ctx = ws.get(f'ctx{tag}', N, D, dt, dev)
-        probs = ws.get(f'probs{tag}', N, H * slots, torch.float32, dev)
         aseed = self._drop_seed() if pattn else 0                  # attention_probs_dropout_prob, modeling_longformer.py:590
-        ops.band_attn_fwd(qkv, lengths_i32, B, Lq, D, H, radius, ctx, probs, row0=row0, drop_p=pattn, drop_seed=aseed)
+        if radius is None:                                         # full attention (BertSelfAttention): per-row log-sum-exp saved instead
+            probs = ws.get(f'lse{tag}', N, H, torch.float32, dev)
+            ops.full_attn_fwd(qkv, lengths_i32, B, Lq, D, H, ctx, probs, row0=row0, drop_p=pattn, drop_seed=aseed)
+        else:
+            probs = ws.get(f'probs{tag}', N, H * slots, torch.float32, dev)
+            ops.band_attn_fwd(qkv, lengths_i32, B, Lq, D, H, radius, ctx, probs, row0=row0, drop_p=pattn, drop_seed=aseed)
         s1 = ws.get(f's1_{tag}', N, D, dt, dev)
         m1 = m2 = None
         wo, bo = self._lt(wf, names, 'wo', D, D), self._lt(pf, names, 'bo', 1, D).view(-1)
@@ -364,9 +368,13 @@ class _TaggerBase(FlatModule):
         dctx = ws.get('dctx', N, D, dt, dev)
         ops.linear_dgrad(ds1d, self._lt(wf, names, 'wo', D, D), dctx)
         dqkv = ws.get('dqkv', N, 3 * D, dt, dev)
-        dsc = ws.get('dsc', N, H * S['slots'], torch.float32, dev)
-        ops.band_attn_bwd(S['qkv'], lengths_i32, S['probs'], dctx, B, Lq, D, H, S['radius'], dqkv, dsc,
-                          dbias=Gv('bqkv', 1, 3 * D).view(-1), row0=row0, drop_p=S['pattn'], drop_seed=S['aseed'])
+        if S['radius'] is None:
+            ops.full_attn_bwd(S['qkv'], lengths_i32, S['probs'], S['ctx'], dctx, B, Lq, D, H, dqkv,
+                              dbias=Gv('bqkv', 1, 3 * D).view(-1), row0=row0, drop_p=S['pattn'], drop_seed=S['aseed'])
+        else:
+            dsc = ws.get('dsc', N, H * S['slots'], torch.float32, dev)
+            ops.band_attn_bwd(S['qkv'], lengths_i32, S['probs'], dctx, B, Lq, D, H, S['radius'], dqkv, dsc,
+                              dbias=Gv('bqkv', 1, 3 * D).view(-1), row0=row0, drop_p=S['pattn'], drop_seed=S['aseed'])
         o_qkv = lay.entries[names['wqkv'][0]][0]
         if self._grad_hook is not None and self.qkv_release == 'projection':
             # data parallel: one weight-gradient GEMM per projection, each third handed to the exchange as soon as it is final --
@@ -412,7 +420,10 @@ class _NativeLoss(torch.autograd.Function):
 # Restricted-window transformer tagger
 # =====================================================================================================
 class Transformer_segmenter(_TaggerBase):
-    """models/CRF.py:508-610 with restricted=True: HF-Longformer-style local attention encoder + linear head."""
+    """models/CRF.py:508-610: encoder + linear head.  restricted=True: HF-Longformer-style local attention (pyramidal windows);
+    restricted=False: the BertModel of Classic_Transformer (models/RestrictedTransformerLayer.py:16-63) -- full attention over
+    each document's valid sentences, positions 0..L-1, attention dropout 0.1 in training (BertConfig's default; dropout_out and
+    window_size are not used there)."""
     grad_hooks_cover_all = True
 
     def __init__(self, tagset_size, embedding_dim, hidden_dim, num_layers=6, nheads=8, dropout_in=0.0, dropout_out=0.0,
@@ -420,8 +431,7 @@ class Transformer_segmenter(_TaggerBase):
                  window_size=127, alpha=0.9, gamma=2, compute_dtype=None, max_position_embedding=4096, seed=None):
         super().__init__()
         self._init_common(loss_fn, threshold, alpha, gamma, compute_dtype)
-        if not restricted:
-            raise NotImplementedError('restricted=False (HF BertModel full attention, models/CRF.py:544) is outside the hot path')
+        self.restricted = bool(restricted)
         # dropout_in -> HF hidden_dropout_prob (embeddings, attention-output and FFN-output dense layers; training mode only),
         # dropout_out -> attention_probs_dropout_prob (RestrictedTransformerLayer.py:88-89)
         if not 0.0 <= float(dropout_in) < 1.0:
@@ -429,13 +439,21 @@ class Transformer_segmenter(_TaggerBase):
         if not 0.0 <= float(dropout_out) < 1.0:
             raise ValueError(f'dropout probability has to be between 0 and 1, but got {dropout_out}')
         self.dropout_in, self.dropout_out = float(dropout_in), float(dropout_out)
+        # attention-probability dropout in training: dropout_out on the restricted path; BertConfig's default 0.1 on the full one
+        # (Classic_Transformer never passes dropout_out on)
+        self._attn_drop = self.dropout_out if self.restricted else 0.1
+        # first position-table row of sentence 0: Longformer's padding_idx + 1 = 2 (restricted), BERT's 0 (full)
+        self._pos_offset = 2 if self.restricted else 0
         self._drop_calls = 0
         self.embedding_dim, self.hidden_dim, self.tagset_size = embedding_dim, hidden_dim, tagset_size
         self.nheads, self.num_layers = nheads, num_layers
-        # pyramidal windows, models/CRF.py:529; every entry must be even, RestrictedTransformerLayer.py:77-80
-        windows = [k * window_size for k in range(num_layers, 0, -1)]
-        assert all(w % 2 == 0 for w in windows), 'All window sizes must be divisible by 2!'
-        self.radii = [w // 2 for w in windows]            # one-sided radius, modeling_longformer.py:478
+        if self.restricted:
+            # pyramidal windows, models/CRF.py:529; every entry must be even, RestrictedTransformerLayer.py:77-80
+            windows = [k * window_size for k in range(num_layers, 0, -1)]
+            assert all(w % 2 == 0 for w in windows), 'All window sizes must be divisible by 2!'
+            self.radii = [w // 2 for w in windows]        # one-sided radius, modeling_longformer.py:478
+        else:
+            self.radii = [None] * num_layers              # None: full attention (window_size is not used)
         if embedding_dim % nheads != 0:
             raise ValueError(f'The hidden size ({embedding_dim}) is not a multiple of the number of attention heads ({nheads})')
         self.n_out = tagset_size if loss_fn == 'CrossEntropy' else 1
@@ -457,7 +475,8 @@ class Transformer_segmenter(_TaggerBase):
         e = 'model.model.embeddings.'
         g = []
         pos = torch.randn(self.max_pos, D, generator=gen) * std
-        pos[1].zero_()                                     # padding_idx = 1
+        if self.restricted:
+            pos[1].zero_()                                 # padding_idx = 1 (BERT's table has none)
         add(g, e + 'position_embeddings.weight', (self.max_pos, D), pos)
         gpos = g
         g = []
@@ -533,7 +552,9 @@ class Transformer_segmenter(_TaggerBase):
         dt, dev = self.compute_dtype, xs.device
         if D != self.embedding_dim:
             raise ValueError(f'expected input dim {self.embedding_dim}, got {D}')
-        if Lq + 2 > self.max_pos:
+        if Lq + self._pos_offset > self.max_pos:
+            if not self.restricted:
+                raise ValueError(f'sequence length {Lq} exceeds max_position_embeddings = {self.max_pos}')
             raise ValueError(f'sequence length {Lq} exceeds max_position_embeddings-2 = {self.max_pos - 2}')
         N, F, H = (pack['n'] if pack else B * Lq), self._ffp, self.nheads
         row_src, row0 = (pack['row_src'], pack['row0']) if pack else (None, None)
@@ -551,7 +572,7 @@ class Transformer_segmenter(_TaggerBase):
         pre0 = ws.get('pre0', N, D, dt, dev)
         mean0 = ws.get('mean0', N, 1, torch.float32, dev)
         rstd0 = ws.get('rstd0', N, 1, torch.float32, dev)
-        ops.embed_layernorm_fwd(x, lay.view(pf, e + 'position_embeddings.weight'), 2,
+        ops.embed_layernorm_fwd(x, lay.view(pf, e + 'position_embeddings.weight'), self._pos_offset,
                                 lay.view(pf, e + 'token_type_embeddings.weight')[0], lay.view(pf, e + 'LayerNorm.weight'),
                                 lay.view(pf, e + 'LayerNorm.bias'), self.ln_eps, h, pre0, mean0, rstd0, row_src=row_src, x2=x2)
         st.update(pre0=pre0, mean0=mean0, rstd0=rstd0)
@@ -565,7 +586,7 @@ class Transformer_segmenter(_TaggerBase):
             last = li == len(self.radii) - 1
             head = (self._w(pf, 'classification.weight'), self._w(pf, 'classification.bias'), scores) if (last and not tail) else None
             S = self._band_layer_fwd(self._layer_names(li), str(li), h, lengths_i32, B, Lq, N, radius, row0, pdrop,
-                                     self.dropout_out if self.training else 0.0, head,
+                                     self._attn_drop if self.training else 0.0, head,
                                      # (a head wider than two outputs takes its parameter gradients from the stored output: _backward_native)
                                      store_out=need_hidden or not last or self.n_out > 2, skip_ln2=last and tail)
             st['layers'].append(S)
@@ -625,12 +646,13 @@ class Transformer_segmenter(_TaggerBase):
             # one pass: LayerNorm backward + the sums that are all anybody wants of its dx -- over the documents of each position into
             # rows [2, L + 2) of the position table, over all rows into token-type row 0 (both OVERWRITTEN; type row 1 is never touched
             # and keeps the zero it was allocated with).  A longer batch earlier may have left rows beyond L + 2: cleared once.
+            off = self._pos_offset
             prev = getattr(self, '_pos_touched', 0)
-            if prev > Lq + 2:
-                pos_g[Lq + 2:prev].zero_()
-            self._pos_touched = Lq + 2
+            if prev > Lq + off:
+                pos_g[Lq + off:prev].zero_()
+            self._pos_touched = Lq + off
             ops.embed_layernorm_bwd(st['pre0'], dh, self._w(pf, e + 'LayerNorm.weight'), st['mean0'], st['rstd0'], B, Lq,
-                                    G(e + 'LayerNorm.weight'), G(e + 'LayerNorm.bias'), type_g[0], pos_g, 2,
+                                    G(e + 'LayerNorm.weight'), G(e + 'LayerNorm.bias'), type_g[0], pos_g, off,
                                     row0=st['pack']['row0'] if st['pack'] else None, lengths=st['lengths'])
         else:
             dpre = ws.get('ds2', N, D, dt, dev)
@@ -640,9 +662,9 @@ class Transformer_segmenter(_TaggerBase):
                               G(e + 'LayerNorm.weight'), G(e + 'LayerNorm.bias'), dxsum=type_g[0])
             # only rows [2, L+2) of the position table ever receive a gradient: keep the rest of its gradient at the zeros it was
             # allocated with and clear what the longest batch so far could have touched
-            self._pos_touched = max(getattr(self, '_pos_touched', 0), Lq + 2)
+            self._pos_touched = max(getattr(self, '_pos_touched', 0), Lq + self._pos_offset)
             pos_g[:self._pos_touched].zero_()
-            ops.embed_bwd(dpre, B, Lq, pos_g, 2, row0=st['pack']['row0'] if st['pack'] else None, lengths=st['lengths'])
+            ops.embed_bwd(dpre, B, Lq, pos_g, self._pos_offset, row0=st['pack']['row0'] if st['pack'] else None, lengths=st['lengths'])
         # embeddings: only the position rows a batch of this length can touch, then type row + LayerNorm
         D_ = self.embedding_dim
         if side is not None:
@@ -650,7 +672,7 @@ class Transformer_segmenter(_TaggerBase):
         p0 = lay.entries[e + 'position_embeddings.weight'][0]
         t0 = lay.entries[e + 'token_type_embeddings.weight'][0]
         assert t0 < p0, 'flat layout: token-type rows and embedding LayerNorm in front of the position table'
-        self._grads_ready(t0, p0 + (Lq + 2) * D_)      # (position rows 0 and 1 ride along: never touched, gradient 0)
+        self._grads_ready(t0, p0 + (Lq + self._pos_offset) * D_)      # (restricted: position rows 0 and 1 ride along, gradient 0)
 
     def _drop_seed(self):
         self._drop_calls += 1
