@@ -75,6 +75,7 @@ const char* mts_version(void);
  * most one workgroup per CU) | 0 ; "band_mfma" = 1 | 0 ; "band_fused_bwd" = 1 (bf16 band attention backward in one pass where it applies:
  * radius <= 15, head dim <= 224) | 0 (two kernels) ; "lstm_parts" = 4 (CU-quad recurrences at H = 256, bf16 and fp32) | 2 (CU pair, bf16) ;
  * "full_mfma" = 1 | 0 (bf16 full attention on the matrix-core kernels where head dim % 32 == 0 and <= 256, else generic) ;
+ * "t5_mfma" = 1 | 0 (bf16 LongT5 local attention on the matrix-core kernels, else generic) ;
  * "lstm_pair_spin_limit" = re-polls before a CU-pair LSTM workgroup gives
  * up on its partner (-1 = default 2^22; tests use 0) ; "lstm_pair_max_pairs" = CU pairs per recurrence launch (1..64, default 64) */
 int mts_set_option(const char* key, int value);
@@ -303,6 +304,59 @@ size_t mts_full_attn_bwd_workspace(int B, int L, int D, int heads);
 int mts_full_attn_bwd(void* stream, int dtype, int B, int L, int D, int heads, float q_scale, const void* qkv,
                       const int32_t* lengths, const float* lse, const void* ctx, const void* dctx, void* dqkv, float* dbias,
                       void* workspace, const int32_t* row0, int n_rows, float drop_p, uint64_t drop_seed);
+
+/* ---------------------------------------------------------------------------------------------
+ * LongT5 local self-attention with a learned, bucketed relative-position bias.
+ * Replaces: LongT5LocalAttention of the LongT5EncoderModel inside RecurrentLongT5 (models/CRF.py:613-762,
+ * models/RestrictedTransformerLayer.py:135-187; HF modeling_longt5.py); plus the backward.
+ * Padded [B, L] layout only.  qkv [B*L, 3*inner] act dtype (columns q | k | v, inner = heads * head_dim, NO 1/sqrt(d) scaling);
+ * lengths int32 [B] (NULL = all L; every lengths[b] >= 1); radius r >= 1 (one-sided); table fp32 [buckets, heads] =
+ * relative_attention_bias.weight; bucket_of_offset int32 [2r + 1]: entry r + (j - i) is the bucket of offset j - i, each in
+ * [0, buckets) (the caller computes it once with the reference's own _relative_position_bucket; kernels never take the log).
+ * ctx [B*L, inner] act dtype.  Per head, s_ij = q_i . k_j + table[bucket_of_offset[r + j - i], h].
+ *   valid query rows i < len_b: softmax over keys j in [i - r, i + r] with 0 <= j < len_b;
+ *   padded query rows len_b <= i < L: every key is masked with -1e10 in the reference, which absorbs the scores in fp32, so the row
+ *   is the uniform mean sum_j v_j / (3 (r + 1)) over j in [(floor(i/(r+1)) - 1)(r+1), (floor(i/(r+1)) + 2)(r+1)) and 0 <= j < L
+ *   (padded v rows included; the reference departs from this only when a padded row's |score| reaches 512).
+ * lse: fp32 [B*L, heads] = log sum_j exp(s_ij) of valid rows (0 on padded rows), saved by the forward; the backward recomputes
+ * P = exp(S - lse) and takes delta = rowsum(dCtx o ctx) from the saved ctx.  Nothing [L, L] or [L, 2r+1] is ever stored.
+ * drop_p > 0: dropout on the probabilities of valid rows (training mode; padded rows are never dropped): what multiplies V is
+ * keep ? p / (1 - drop_p) : 0 with
+ *     keep = mts_hash32(drop_seed, ((uint64_t)(b * L + i) * heads + h) * (2r + 1) + (r + j - i)) >= (uint32_t)max(1, min(2^32 - 1, drop_p * 2^32))
+ * (mts_hash32: csrc/common.h).  The backward, given the same drop_p / drop_seed, regenerates it.
+ * mts_t5_local_attn_bwd: dqkv [B*L, 3*inner] act dtype, every row written: padded query rows carry no gradient (they never reach a
+ * valid row or the loss) -- their dq is 0 and their dctx is NOT read; dk = dv = 0 for padded keys.  dtable fp32 [buckets, heads]
+ * OVERWRITTEN: per-workgroup sums of dS per (head, offset) go to the workspace, one kernel sums them per (head, offset) in a fixed
+ * order, another adds the offsets of each bucket in ascending offset; buckets no offset maps to get exactly 0.  workspace (REQUIRED)
+ * of mts_t5_local_attn_bwd_workspace(B, L, heads, radius) bytes.  No atomics: bitwise reproducible.
+ * Covered: head_dim 64 (LongT5's d_kv), radius <= 1024, fp32 and bf16; qkv, ctx, dctx and dqkv 16-byte aligned (rows are 16-byte
+ * vectors); anything else is MTS_ERR_UNSUPPORTED before any launch.  bf16 runs on matrix-core kernels (v_mfma_f32_16x16x32_bf16);
+ * mts_set_option("t5_mfma", 0) sends it to the generic kernels (v_dot2_f32_bf16), which also serve fp32.
+ * ------------------------------------------------------------------------------------------- */
+int mts_t5_local_attn_fwd(void* stream, int dtype, int B, int L, int heads, int head_dim, int radius, const void* qkv,
+                          const int32_t* lengths, const float* table, int buckets, const int32_t* bucket_of_offset, void* ctx,
+                          float* lse, float drop_p, uint64_t drop_seed);
+size_t mts_t5_local_attn_bwd_workspace(int B, int L, int heads, int radius);
+int mts_t5_local_attn_bwd(void* stream, int dtype, int B, int L, int heads, int head_dim, int radius, const void* qkv,
+                          const int32_t* lengths, const float* table, int buckets, const int32_t* bucket_of_offset,
+                          const float* lse, const void* ctx, const void* dctx, void* dqkv, float* dtable, void* workspace,
+                          float drop_p, uint64_t drop_seed);
+
+/* ---------------------------------------------------------------------------------------------
+ * RMSNorm (T5LayerNorm: no mean subtraction, no bias).  Replaces the layer_norm / final_layer_norm of LongT5 (HF modeling_longt5.py
+ * LongT5LayerNorm) inside RecurrentLongT5, and its backward.
+ * x, y [rows, D] act dtype; w fp32 [D]; y = w * (x * rstd), rstd = 1 / sqrt(mean(x^2) + eps) computed in fp32; rstd fp32 [rows]
+ * (saved for the backward; may be NULL in the forward).  D a multiple of 4, <= 2048; activations aligned to 4 elements (16 B fp32,
+ * 8 B bf16) and w to 16 bytes (else MTS_ERR_UNSUPPORTED).
+ * mts_rmsnorm_bwd: dx = rstd (dy w - n mean(dy w . n)) (+ dres), n = x rstd; dres (optional, act dtype [rows, D]) is the residual
+ * branch's gradient, and dx may alias it (not x or dy).  dw fp32 [D] = sum_rows dy n, OVERWRITTEN: per-workgroup partial rows in the
+ * workspace (mts_rmsnorm_bwd_workspace(rows, D) bytes, REQUIRED), then one fixed-order reduce (as mts_layernorm_bwd): bitwise
+ * reproducible.
+ * ------------------------------------------------------------------------------------------- */
+int mts_rmsnorm_fwd(void* stream, int dtype, int rows, int D, const void* x, const float* w, float eps, void* y, float* rstd);
+size_t mts_rmsnorm_bwd_workspace(int rows, int D);
+int mts_rmsnorm_bwd(void* stream, int dtype, int rows, int D, const void* x, const void* dy, const void* dres, const float* w,
+                    const float* rstd, void* dx, float* dw, void* workspace);
 
 /* ---------------------------------------------------------------------------------------------
  * Tagger head tail: loss + its gradient, and greedy decode.

@@ -9,7 +9,8 @@ from .datasets import load_dataset_for_inference, load_dataset_from_precomputed,
 from .lightning_model import TextSegmenter  # noqa: F401
 from .prefetch import DevicePrefetcher  # noqa: F401
 from .rnn_taggers import BiLSTM, BiLSTMLateFusion, BiRnnCrf  # noqa: F401
+from .t5_taggers import RecurrentLongT5  # noqa: F401
 from .taggers import RestrictedTransformerEncoderLayer, Transformer_segmenter  # noqa: F401
 
-__all__ = ['TextSegmenter', 'Transformer_segmenter', 'BiLSTM', 'BiLSTMLateFusion', 'BiRnnCrf', 'AudioPortionDataset',
+__all__ = ['TextSegmenter', 'Transformer_segmenter', 'BiLSTM', 'BiLSTMLateFusion', 'BiRnnCrf', 'RecurrentLongT5', 'AudioPortionDataset',
            'AudioPortionDatasetInference', 'RestrictedTransformerEncoderLayer', 'DevicePrefetcher']

@@ -82,6 +82,12 @@ SIGNATURES = {
     'mts_full_attn_fwd': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, C.c_uint64]),
     'mts_full_attn_bwd_workspace': (_sz, [_i, _i, _i, _i]),
     'mts_full_attn_bwd': (_i, [_vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, C.c_uint64]),
+    'mts_t5_local_attn_fwd': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _f, C.c_uint64]),
+    'mts_t5_local_attn_bwd_workspace': (_sz, [_i, _i, _i, _i]),
+    'mts_t5_local_attn_bwd': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, C.c_uint64]),
+    'mts_rmsnorm_fwd': (_i, [_vp, _i, _i, _i, _vp, _vp, _f, _vp, _vp]),
+    'mts_rmsnorm_bwd_workspace': (_sz, [_i, _i]),
+    'mts_rmsnorm_bwd': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'mts_tagger_loss_workspace': (_sz, [_i, _i]),
     'mts_tagger_loss': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _sz, _vp, _i]),
     'mts_greedy_decode': (_i, [_vp, _i, _i, _i, _vp, _vp, _f, _vp]),

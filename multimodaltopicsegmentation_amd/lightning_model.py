@@ -13,6 +13,7 @@ import torch.nn as nn
 
 from . import metrics
 from .rnn_taggers import BiLSTM, BiLSTMLateFusion, BiRnnCrf
+from .t5_taggers import RecurrentLongT5
 from .taggers import Transformer_segmenter
 
 try:  # pragma: no cover - not installed in the build image
@@ -42,7 +43,7 @@ except Exception:  # noqa: BLE001
             return obj
 
 # architectures of the reference that are outside the hot path
-_OUT_OF_SCOPE = ('SimpleBiLSTM', 'MLP', 'Transformer-CRF', 'RecurrentLongT5', 'BiLSTMRestrictedMHA', 'SwitchBiLSTM', 'SheikhBiLSTM')
+_OUT_OF_SCOPE = ('SimpleBiLSTM', 'MLP', 'Transformer-CRF', 'BiLSTMRestrictedMHA', 'SwitchBiLSTM', 'SheikhBiLSTM')
 
 
 class TextSegmenter(_Base):
@@ -79,6 +80,10 @@ class TextSegmenter(_Base):
                                                positional_encoding=positional_encoding, nheads=nheads, threshold=threshold,
                                                alpha=alpha, gamma=gamma, window_size=attention_window, compute_dtype=compute_dtype,
                                                restricted=restricted)
+        elif architecture == 'RecurrentLongT5':
+            self.model = RecurrentLongT5(tagset_size, embedding_dim, hidden_dim, num_layers=num_layers, dropout_in=dropout_in,
+                                         dropout_out=dropout_out, batch_first=batch_first, loss_fn=loss_fn, nheads=nheads, threshold=threshold,
+                                         alpha=alpha, gamma=gamma, window_size=attention_window, compute_dtype=compute_dtype)
         elif architecture == 'BiLSTMLateFusion':
             self.model = BiLSTMLateFusion(tagset_size, embedding_dim, hidden_dim, num_layers=num_layers, bidirectional=bidirectional,
                                           dropout_in=dropout_in, dropout_out=dropout_out, batch_first=batch_first, LSTM=LSTM,

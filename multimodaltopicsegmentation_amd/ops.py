@@ -341,6 +341,36 @@ def full_attn_bwd(qkv, lengths, lse, ctx, dctx, B, Lq, D, heads, dqkv, dbias=Non
                                     qkv.shape[0] if row0 is not None else 0, float(drop_p), int(drop_seed)))
 
 
+def t5_local_attn_fwd(qkv, lengths, B, Lq, heads, radius, table, bucket_of_offset, ctx, lse, drop_p=0.0, drop_seed=0):
+    """LongT5 local attention (include/mts.h): qkv [B*Lq, 3*heads*64], table fp32 [buckets, heads], bucket_of_offset int32 [2r+1];
+    lse (fp32 [B*Lq, heads]) receives the per-row log-sum-exp."""
+    with _timed(('t5_fwd', B, Lq, heads, radius)):
+        check(lib.mts_t5_local_attn_fwd(stream_ptr(), dtype_code(qkv.dtype), B, Lq, heads, 64, radius, ptr(qkv), ptr(lengths), ptr(table),
+                                        table.shape[0], ptr(bucket_of_offset), ptr(ctx), ptr(lse), float(drop_p), int(drop_seed)))
+
+
+def t5_local_attn_bwd(qkv, lengths, B, Lq, heads, radius, table, bucket_of_offset, lse, ctx, dctx, dqkv, dtable, drop_p=0.0, drop_seed=0):
+    """Backward of t5_local_attn_fwd: dqkv (every row written) and dtable fp32 [buckets, heads] (overwritten)."""
+    ws = _scratch(lib.mts_t5_local_attn_bwd_workspace(B, Lq, heads, radius), qkv.device, 't5_bwd')
+    with _timed(('t5_bwd', B, Lq, heads, radius)):
+        check(lib.mts_t5_local_attn_bwd(stream_ptr(), dtype_code(qkv.dtype), B, Lq, heads, 64, radius, ptr(qkv), ptr(lengths), ptr(table),
+                                        table.shape[0], ptr(bucket_of_offset), ptr(lse), ptr(ctx), ptr(dctx), ptr(dqkv), ptr(dtable),
+                                        ptr(ws), float(drop_p), int(drop_seed)))
+
+
+def rmsnorm_fwd(x, w, eps, y, rstd):
+    rows, D = x.shape
+    check(lib.mts_rmsnorm_fwd(stream_ptr(), dtype_code(x.dtype), rows, D, ptr(x), ptr(w), float(eps), ptr(y), ptr(rstd)))
+
+
+def rmsnorm_bwd(x, dy, w, rstd, dx, dw, dres=None):
+    """dx = RMSNorm backward (+ dres; dx may be dres itself); dw fp32 [D] overwritten."""
+    rows, D = x.shape
+    ws = _scratch(lib.mts_rmsnorm_bwd_workspace(rows, D), x.device, 'rms_bwd')
+    check(lib.mts_rmsnorm_bwd(stream_ptr(), dtype_code(x.dtype), rows, D, ptr(x), ptr(dy), ptr(dres), ptr(w), ptr(rstd), ptr(dx), ptr(dw),
+                              ptr(ws)))
+
+
 def tagger_loss(kind, scores, targets, lengths, alpha, gamma, loss_out, dscores, row_src=None, batch_shape=None):
     """scores [B, L, n_out]; or, for a packed batch, [n_rows, n_out] with row_src (int32 [n_rows]) and batch_shape = (B, L)."""
     if row_src is None:
