@@ -359,6 +359,22 @@ int mts_rmsnorm_bwd(void* stream, int dtype, int rows, int D, const void* x, con
                     const float* rstd, void* dx, float* dw, void* workspace);
 
 /* ---------------------------------------------------------------------------------------------
+ * Adjacent-pair bilinear score.  Replaces the tail of SheikhBiLSTM (models/CRF.py:1009-1014 in loss, :1029-1035 in forward):
+ * (x_for[:, :-1] * x_bac[:, 1:]).sum(2) and the appended step of ones.
+ * F, G: [B*L, H] act dtype with leading dimensions ldf, ldg in ELEMENTS (they may be the two halves of one [B*L, 2H] buffer);
+ * scores, dscores: fp32 [B, L].
+ * forward: scores[b, t] = sum_h F[bL + t, h] G[bL + t + 1, h] for t < L - 1 (fp32 accumulation), scores[b, L - 1] = 1.0f exactly; a
+ * pair never crosses a document.
+ * backward: dF[b, t, :] = dscores[b, t] G[b, t + 1, :] (exactly 0 at t = L - 1), dG[b, t, :] = dscores[b, t - 1] F[b, t - 1, :]
+ * (exactly 0 at t = 0); every row of dF and dG is OVERWRITTEN, dscores[b, L - 1] is never read; no atomics, bitwise reproducible.
+ * Covered: H a multiple of 8 (bf16) / 4 (fp32); F, G, dF, dG and their leading dimensions 16-byte aligned; anything else is
+ * MTS_ERR_UNSUPPORTED before any launch.  B * L == 0 returns MTS_OK without a launch; L == 1 is valid (all scores 1, dF = dG = 0).
+ * ------------------------------------------------------------------------------------------- */
+int mts_pair_score_fwd(void* stream, int dtype, int B, int L, int H, const void* F, int ldf, const void* G, int ldg, float* scores);
+int mts_pair_score_bwd(void* stream, int dtype, int B, int L, int H, const void* F, int ldf, const void* G, int ldg,
+                       const float* dscores, void* dF, int lddf, void* dG, int lddg);
+
+/* ---------------------------------------------------------------------------------------------
  * Tagger head tail: loss + its gradient, and greedy decode.
  * Replaces: the un-pad loop + BCE/Focal/CE of models/CRF.py:342-356 (=:447-461, :581-595),
  * models/focal_loss.py:38-57, and decode models/CRF.py:362-369.

@@ -88,6 +88,8 @@ SIGNATURES = {
     'mts_rmsnorm_fwd': (_i, [_vp, _i, _i, _i, _vp, _vp, _f, _vp, _vp]),
     'mts_rmsnorm_bwd_workspace': (_sz, [_i, _i]),
     'mts_rmsnorm_bwd': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'mts_pair_score_fwd': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
+    'mts_pair_score_bwd': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i]),
     'mts_tagger_loss_workspace': (_sz, [_i, _i]),
     'mts_tagger_loss': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _sz, _vp, _i]),
     'mts_greedy_decode': (_i, [_vp, _i, _i, _i, _vp, _vp, _f, _vp]),

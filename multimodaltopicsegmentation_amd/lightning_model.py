@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 
 from . import metrics
-from .rnn_taggers import BiLSTM, BiLSTMLateFusion, BiRnnCrf
+from .rnn_taggers import BiLSTM, BiLSTMLateFusion, BiRnnCrf, SheikhBiLSTM
 from .t5_taggers import RecurrentLongT5
 from .taggers import Transformer_segmenter
 
@@ -43,7 +43,7 @@ except Exception:  # noqa: BLE001
             return obj
 
 # architectures of the reference that are outside the hot path
-_OUT_OF_SCOPE = ('SimpleBiLSTM', 'MLP', 'Transformer-CRF', 'BiLSTMRestrictedMHA', 'SwitchBiLSTM', 'SheikhBiLSTM')
+_OUT_OF_SCOPE = ('SimpleBiLSTM', 'MLP', 'Transformer-CRF', 'BiLSTMRestrictedMHA', 'SwitchBiLSTM')
 
 
 class TextSegmenter(_Base):
@@ -89,6 +89,11 @@ class TextSegmenter(_Base):
                                           dropout_in=dropout_in, dropout_out=dropout_out, batch_first=batch_first, LSTM=LSTM,
                                           loss_fn=loss_fn, threshold=threshold, alpha=alpha, gamma=gamma, compute_dtype=compute_dtype)
             self.double_input = True
+        elif architecture == 'SheikhBiLSTM':
+            # lightning_model.py:245-247: dropout_in 0.5 (live in eval mode too), dropout_attention 0 and batch_first are hard-wired;
+            # the user's dropout_in, loss_fn, threshold, alpha and gamma are not passed on
+            self.model = SheikhBiLSTM(tagset_size, embedding_dim, hidden_dim, num_layers=num_layers, dropout_in=0.5, dropout_attention=0,
+                                      batch_first=True, compute_dtype=compute_dtype)
         elif architecture in _OUT_OF_SCOPE:
             if architecture == 'SwitchBiLSTM' and switch == 'bias':
                 raise NotImplementedError()                                  # lightning_model.py:235

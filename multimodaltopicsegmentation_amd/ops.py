@@ -371,6 +371,22 @@ def rmsnorm_bwd(x, dy, w, rstd, dx, dw, dres=None):
                               ptr(ws)))
 
 
+def pair_score_fwd(F, G, B, Lq, scores):
+    """scores[b, t] = F[b, t] . G[b, t + 1] for t < Lq - 1, 1.0 at t = Lq - 1 (include/mts.h).  F, G: [B*Lq, H] views in the activation
+    dtype (row strides free: the two halves of one buffer); scores fp32 [B, Lq]."""
+    H = F.shape[1]
+    with _timed(('pair_fwd', B, Lq, H)):
+        check(lib.mts_pair_score_fwd(stream_ptr(), dtype_code(F.dtype), B, Lq, H, ptr(F), F.stride(0), ptr(G), G.stride(0), ptr(scores)))
+
+
+def pair_score_bwd(F, G, dscores, B, Lq, dF, dG):
+    """Backward of pair_score_fwd: every row of dF and dG is overwritten (dscores[b, Lq - 1] is never read)."""
+    H = F.shape[1]
+    with _timed(('pair_bwd', B, Lq, H)):
+        check(lib.mts_pair_score_bwd(stream_ptr(), dtype_code(F.dtype), B, Lq, H, ptr(F), F.stride(0), ptr(G), G.stride(0), ptr(dscores),
+                                     ptr(dF), dF.stride(0), ptr(dG), dG.stride(0)))
+
+
 def tagger_loss(kind, scores, targets, lengths, alpha, gamma, loss_out, dscores, row_src=None, batch_shape=None):
     """scores [B, L, n_out]; or, for a packed batch, [n_rows, n_out] with row_src (int32 [n_rows]) and batch_shape = (B, L)."""
     if row_src is None:

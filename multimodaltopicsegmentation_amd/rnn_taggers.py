@@ -563,3 +563,134 @@ class BiRnnCrf(_RnnTaggerBase):
             L.check_async()            # synchronised by the copy: report a CU-pair LSTM timeout of this forward instead of its paths
             lens = [int(v) for v in (lenghts.tolist() if lenghts is not None else [Lq] * B)]
         return score, [ph[i, :min(lens[i], Lq)].tolist() for i in range(B)]
+
+
+_PAIR_LENGTHS_CACHE = {}
+
+
+class SheikhBiLSTM(_RnnTaggerBase):
+    """models/CRF.py:980-1041: Sheikh et al.'s change-detection BiLSTM.  The boundary after sentence t is scored from the forward state at
+    t and the backward state at t + 1:  s[b, t] = forward_dense(h[b, t, :H]) . backward_dense(h[b, t + 1, H:]),  t < max(len) - 1, and
+    ``forward`` appends one step of ones.  Loss: BCELoss(1 - sigmoid(s), 1 - y) over t < len_b - 1 (= BCE on (s, y); whatever ``loss_fn``
+    says, :1002 overwrites it).  ``.th`` is never set by the constructor (TextSegmenter.test_step assigns it): ``forward`` before that
+    raises the reference's AttributeError.  The reference's ``classification`` Linear(2H, 1) is read by no method: this module does not own
+    it and drops it on load."""
+    grad_hooks_cover_all = False     # gradients are not announced span by span: NativeTrainer all-reduces after the backward
+    DEAD_KEYS = ('classification.weight', 'classification.bias')
+
+    def __init__(self, tagset_size, embedding_dim, hidden_dim, num_layers, dropout_in=0.5, dropout_attention=0.0, batch_first=True,
+                 loss_fn='BinaryCrossEntropy', alpha=0.9, gamma=2, compute_dtype=None, seed=None):
+        super().__init__()
+        if loss_fn not in ('BinaryCrossEntropy', 'FocalLoss'):
+            raise ValueError('Choose one of FocalLoss or BinaryCrossEntropy as loss function')    # models/CRF.py:999
+        self._init_common('BinaryCrossEntropy', None, alpha, gamma, compute_dtype)                # :1002: nn.BCELoss in both cases
+        del self.th                                                                               # the reference's constructor never sets it
+        self._check_rnn_args(dropout_in, dropout_attention, True, True)                           # RNN(..., dropout_in, dropout_attention, LSTM=True)
+        self.embedding_dim, self.hidden_dim, self.tagset_size, self.num_layers = embedding_dim, hidden_dim, tagset_size, num_layers
+        self.n_out = 1
+        gen = torch.Generator().manual_seed(torch.initial_seed() if seed is None else seed)
+        groups, init, pads = _rnn_groups('lstm.', embedding_dim, hidden_dim, num_layers, gen)
+        H, Hp = hidden_dim, round_up(hidden_dim, 8)
+        self._hp = Hp
+        fw, fb = _linear_init(H, H, gen)
+        bw, bb = _linear_init(H, H, gen)
+        groups.append([('forward_dense.weight', (Hp, Hp))])
+        groups.append([('backward_dense.weight', (Hp, Hp))])
+        groups.append([('forward_dense.bias', (Hp,)), ('backward_dense.bias', (Hp,))])   # adjacent: one column sum over dF | dG gives both
+        init.update({'forward_dense.weight': fw, 'forward_dense.bias': fb, 'backward_dense.weight': bw, 'backward_dense.bias': bb})
+        if Hp != H:                                    # padded units are inert: zero rows / columns / biases -> F, G and their gradients are 0 there
+            for n in ('forward_dense', 'backward_dense'):
+                pads[n + '.weight'] = [(0, 1, H, Hp), (1, 1, H, Hp)]
+                pads[n + '.bias'] = [(0, 1, H, Hp)]
+        self._init_flat(FlatLayout(groups, pads), init)
+        self._rnn = _RnnStack(self, 'lstm.', embedding_dim, hidden_dim, num_layers, 'r')
+        self._register_load_state_dict_pre_hook(self._drop_dead_keys)
+
+    @staticmethod
+    def _drop_dead_keys(state_dict, prefix, *args):
+        """A reference checkpoint carries classification.{weight,bias} (Linear(2H, 1), :994 / :997), which no method reads: ignore them."""
+        for k in SheikhBiLSTM.DEAD_KEYS:
+            state_dict.pop(prefix + k, None)
+
+    @staticmethod
+    def _pair_lengths(lengths, li32):
+        """max(len - 1, 0) per document on the device: the rows the loss averages.  Cached next to taggers._prep_lengths' entry (one small
+        upload per distinct host length vector, none per step)."""
+        if lengths is None or not (lengths.device.type == 'cpu' and lengths.numel() <= 4096):
+            return (li32 - 1).clamp_(min=0)
+        key = (tuple(lengths.tolist()), str(li32.device))
+        hit = _PAIR_LENGTHS_CACHE.get(key)
+        if hit is None:
+            if len(_PAIR_LENGTHS_CACHE) > 64:
+                _PAIR_LENGTHS_CACHE.clear()
+            hit = _PAIR_LENGTHS_CACHE[key] = (lengths.to(torch.int32) - 1).clamp_(min=0).to(li32.device).contiguous()
+        return hit
+
+    def _fwd(self, xs, lengths):
+        x, Lq = self._prep_input(xs, lengths)
+        first = x[0] if isinstance(x, tuple) else x
+        B, dev, Hp = first.shape[0], first.device, self._hp
+        li32 = self._prep_lengths(lengths, B, Lq, dev)
+        h, saved = self._rnn.forward(self._drop_in(self._to_act(x), 'r'), li32, B, Lq)
+        h, hmask = self._drop_out(h, 'r')
+        wf, pf = self._weights(), self._flat
+        # F = forward_dense(forward states) | G = backward_dense(backward states): the two halves of one [N, 2Hp] buffer, every row (the
+        # reference's x[:, :-1] / x[:, 1:] slices are the pairing of the score kernel)
+        FG = self._ws.get('FG', B * Lq, 2 * Hp, self.compute_dtype, dev)
+        ops.linear_fwd(h[:, :Hp], self._w(wf, 'forward_dense.weight'), self._w(pf, 'forward_dense.bias'), FG[:, :Hp])
+        ops.linear_fwd(h[:, Hp:], self._w(wf, 'backward_dense.weight'), self._w(pf, 'backward_dense.bias'), FG[:, Hp:])
+        scores = self._ws.get('scores', B * Lq, 1, torch.float32, dev)
+        ops.pair_score_fwd(FG[:, :Hp], FG[:, Hp:], B, Lq, scores)
+        return dict(B=B, L=Lq, li32=li32, h=h, hmask=hmask, saved=saved, FG=FG, scores=scores.view(B, Lq, 1))
+
+    def loss_and_grad(self, xs, lengths, tags, want_grad=True):
+        L.require_gpu()
+        st = self._fwd(xs, lengths)
+        dev, B, Lq, Hp = st['scores'].device, st['B'], st['L'], self._hp
+        tg = tags.to(device=dev, dtype=torch.float32).contiguous()
+        loss_out = torch.empty(2, dtype=torch.float32, device=dev)
+        dsc = self._ws.get('dscores', B * Lq, 1, torch.float32, dev) if want_grad else None
+        # the un-pad loop of :1016-1019 keeps t < len_b - 1; mts_tagger_loss writes 0 into dscores for every row it does not average
+        ops.tagger_loss(L.LOSS_BCE, st['scores'], tg, self._pair_lengths(lengths, st['li32']), self.alpha, self.gamma, loss_out, dsc)
+        if Lq <= 1:
+            loss_out[:1].fill_(float('nan'))           # every document of length <= 1: BCELoss over an empty tensor is NaN upstream (the
+                                                       # kernel's mean over zero rows is 0); dscores is all zero, and so is every gradient
+        if want_grad:
+            ops.scale_(dsc, self.loss_grad_scale)
+            g, lay, wf = self.grad_flat(), self._layout, self._weights()
+            FG, h = st['FG'], st['h']
+            dFG = self._ws.get('dFG', B * Lq, 2 * Hp, self.compute_dtype, dev)
+            ops.pair_score_bwd(FG[:, :Hp], FG[:, Hp:], dsc, B, Lq, dFG[:, :Hp], dFG[:, Hp:])
+            off, n = lay.span('forward_dense.bias', 'backward_dense.bias')
+            ops.colsum(dFG, g[off:off + n])
+            ops.linear_wgrad(dFG[:, :Hp], h[:, :Hp], lay.view(g, 'forward_dense.weight'))
+            ops.linear_wgrad(dFG[:, Hp:], h[:, Hp:], lay.view(g, 'backward_dense.weight'))
+            dout = self._ws.get('dout', B * Lq, 2 * Hp, self.compute_dtype, dev)
+            ops.linear_dgrad(dFG[:, :Hp], self._w(wf, 'forward_dense.weight'), dout[:, :Hp])
+            ops.linear_dgrad(dFG[:, Hp:], self._w(wf, 'backward_dense.weight'), dout[:, Hp:])
+            if st['hmask'] is not None:
+                ops.dropout_bwd(dout, dout, st['hmask'], self.dropout_out)
+            self._rnn.backward(st['saved'], dout, st['li32'], B, Lq)
+        return loss_out[0], st['scores']
+
+    def loss(self, inputs, lengths, tags):
+        """models/CRF.py:1005-1023 (no ``segments`` argument: TextSegmenter.training_step falls back on the TypeError, as upstream)."""
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self._flat_params.values()):
+            return self._autograd_loss(lambda: self.loss_and_grad(inputs, lengths, tags, True)[0])
+        return self.loss_and_grad(inputs, lengths, tags, False)[0].clone()
+
+    def forward(self, inputs, lenghts, threshold=0.4):
+        """models/CRF.py:1025-1041: scores [B, max(len), 1] with the appended step of ones, and the lists of 1 - sigmoid(s) < th."""
+        if self.th is not None:                        # AttributeError until .th is assigned, as upstream (:1036)
+            threshold = self.th
+        L.require_gpu()
+        with torch.no_grad():
+            st = self._fwd(inputs, lenghts)
+            scores = st['scores'].clone()
+            B, Lq, _ = scores.shape
+            tags = torch.empty(B, Lq, dtype=torch.uint8, device=scores.device)
+            ops.greedy_decode(scores, st['li32'], 1.0 - threshold, tags)     # sigmoid(s) > 1 - th  <=>  1 - sigmoid(s) < th, strict
+            tags_h = tags.cpu().numpy().astype(bool)
+            L.check_async()
+            lens = [int(v) for v in (lenghts.tolist() if lenghts is not None else [Lq] * B)]
+        return scores, [tags_h[i, :lens[i]].tolist() for i in range(B)]
