@@ -451,6 +451,35 @@ int mts_adam_step(void* stream, size_t n, float* param, const float* grad, float
                   float lr, float beta1, float beta2, float eps, int step, float grad_scale, void* bf16_copy);
 int mts_sgd_step(void* stream, size_t n, float* param, const float* grad, float* momentum_buf, float lr,
                  float momentum, float weight_decay, int first_step, float grad_scale, void* bf16_copy);
+/* GRADIENT CLIPPING inside the optimizer pass.  Replaces what Lightning's Trainer(gradient_clip_val, gradient_clip_algorithm)
+ * (train_fit.py:288,295,779) does between backward and optimizer.step(): torch.nn.utils.clip_grad_norm_ / clip_grad_value_.
+ *
+ * mts_grad_norm: norm_out[0] = || grad_scale * grad ||_2 over n_spans (1..4) spans [span_begin_host[s], span_end_host[s]) (in ELEMENTS
+ * of `grad`, host arrays read before the call returns) of the flat fp32 gradient -- the same grad_scale the optimizer applies, so
+ * the norm is that of the averaged gradient.  norm_out is a DEVICE fp32 scalar the clipped steps below read on the same stream;
+ * the host never sees it.  Two launches: per-workgroup partial sums of squares STORED to `workspace` (mts_grad_norm_workspace()
+ * bytes, REQUIRED), then one workgroup adds them in a fixed order and takes the square root.  No atomics: bitwise reproducible.
+ * A NaN / Inf element gives a NaN / Inf norm.  Every span must begin on a 16-byte boundary (MTS_ERR_INVALID before any launch
+ * otherwise); any length.  All spans empty: MTS_OK without a launch, norm_out is not written (a zeroed scalar stays 0).
+ *
+ * mts_adam_step_clipped / mts_sgd_step_clipped: mts_adam_step / mts_sgd_step with gr = clip(grad * grad_scale) in place of
+ * grad * grad_scale (SGD adds the weight decay AFTER clipping, as torch does when .grad is clipped before step()).
+ *   norm mode  (total_norm != NULL, clip_value == 0): gr = (grad * grad_scale) * coef, coef = min(1, max_norm / (*total_norm + 1e-6))
+ *              read from device memory; a NaN norm gives a NaN coef.  coef == 1 gives the bits of the unclipped entry points.
+ *              clip_coef_out (optional, device fp32 scalar) receives coef.
+ *   value mode (total_norm == NULL, clip_value > 0): gr = clamp(grad * grad_scale, -clip_value, +clip_value); a NaN stays NaN.
+ * Before any device work: null operands, max_norm < 0 (or NaN), clip_value < 0, neither or both modes selected, and operands that
+ * are not aligned (Adam: param, grad and moments to 16 bytes, bf16_copy to 8 -- the vector accesses of the kernel) are
+ * MTS_ERR_INVALID.  n == 0: MTS_OK without a launch. */
+size_t mts_grad_norm_workspace(void);
+int mts_grad_norm(void* stream, const float* grad, int n_spans, const size_t* span_begin_host, const size_t* span_end_host,
+                  float grad_scale, float* workspace, float* norm_out);
+int mts_adam_step_clipped(void* stream, size_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
+                          float lr, float beta1, float beta2, float eps, int step, float grad_scale, void* bf16_copy,
+                          const float* total_norm, float max_norm, float clip_value, float* clip_coef_out);
+int mts_sgd_step_clipped(void* stream, size_t n, float* param, const float* grad, float* momentum_buf, float lr,
+                         float momentum, float weight_decay, int first_step, float grad_scale, void* bf16_copy,
+                         const float* total_norm, float max_norm, float clip_value, float* clip_coef_out);
 /* x[0..n) *= scale (fp32).  Token-weighted data parallelism: the reference's loss is a mean over the LOCAL batch's valid
  * sentences (models/CRF.py:352); multiplying d loss / d scores by world * n_local / n_global before the SUM all-reduce (and
  * grad_scale = 1/world in the optimizer) gives the single-process gradient of the global batch. */

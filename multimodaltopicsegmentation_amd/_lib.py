@@ -106,6 +106,10 @@ SIGNATURES = {
     'mts_crf_viterbi': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     'mts_adam_step': (_i, [_vp, _sz, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i, _f, _vp]),
     'mts_sgd_step': (_i, [_vp, _sz, _vp, _vp, _vp, _f, _f, _f, _i, _f, _vp]),
+    'mts_grad_norm_workspace': (_sz, []),
+    'mts_grad_norm': (_i, [_vp, _vp, _i, _vp, _vp, _f, _vp, _vp]),
+    'mts_adam_step_clipped': (_i, [_vp, _sz, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i, _f, _vp, _vp, _f, _f, _vp]),
+    'mts_sgd_step_clipped': (_i, [_vp, _sz, _vp, _vp, _vp, _f, _f, _f, _i, _f, _vp, _vp, _f, _f, _vp]),
     'mts_scale': (_i, [_vp, _sz, _vp, _f]),
     'mts_collate_pad': (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _f, _i]),
 }

@@ -463,6 +463,40 @@ def sgd_step(param, grad, buf, lr, momentum, weight_decay, first_step, grad_scal
                            int(first_step), grad_scale, ptr(bf16_copy)))
 
 
+def grad_norm_workspace(device):
+    """fp32 workspace for grad_norm (the per-workgroup partial sums)."""
+    return torch.empty(lib.mts_grad_norm_workspace() // 4, dtype=torch.float32, device=device)
+
+
+def grad_norm(grad, spans, grad_scale, workspace, out):
+    """out (0-d or 1-element fp32 DEVICE tensor) = || grad_scale * grad ||_2 over spans [(a, b), ...] of the flat fp32 gradient;
+    no host synchronisation, bitwise reproducible (include/mts.h: mts_grad_norm).  Every a must be a multiple of 4 elements."""
+    assert grad.dtype == torch.float32 and grad.is_contiguous() and out.dtype == torch.float32 and workspace.dtype == torch.float32
+    assert workspace.numel() * 4 >= lib.mts_grad_norm_workspace()
+    if not any(b > a for a, b in spans):
+        out.zero_()
+        return out
+    begin = (ctypes.c_size_t * len(spans))(*[a for a, _ in spans])
+    end = (ctypes.c_size_t * len(spans))(*[b for _, b in spans])
+    check(lib.mts_grad_norm(stream_ptr(), ptr(grad), len(spans), begin, end, grad_scale, ptr(workspace), ptr(out)))
+    return out
+
+
+def adam_step_clipped(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, grad_scale=1.0, bf16_copy=None, total_norm=None,
+                      max_norm=0.0, clip_value=0.0, clip_coef_out=None):
+    """adam_step on the clipped gradient: total_norm (device scalar from grad_norm) + max_norm = clip_grad_norm_, or clip_value =
+    clip_grad_value_; clip_coef_out (device scalar, optional) receives the norm mode's coefficient."""
+    check(lib.mts_adam_step_clipped(stream_ptr(), param.numel(), ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), lr, beta1, beta2,
+                                    eps, step, grad_scale, ptr(bf16_copy), ptr(total_norm), max_norm, clip_value, ptr(clip_coef_out)))
+
+
+def sgd_step_clipped(param, grad, buf, lr, momentum, weight_decay, first_step, grad_scale=1.0, bf16_copy=None, total_norm=None,
+                     max_norm=0.0, clip_value=0.0, clip_coef_out=None):
+    """sgd_step on the clipped gradient (the weight decay is added after clipping); arguments as adam_step_clipped."""
+    check(lib.mts_sgd_step_clipped(stream_ptr(), param.numel(), ptr(param), ptr(grad), ptr(buf), lr, momentum, weight_decay,
+                                   int(first_step), grad_scale, ptr(bf16_copy), ptr(total_norm), max_norm, clip_value, ptr(clip_coef_out)))
+
+
 def scale_(x, scale):
     """x *= scale in place (fp32, contiguous)."""
     if scale != 1.0:

@@ -10,6 +10,7 @@ This is the MI355X-first replacement for what Lightning does around ``TextSegmen
   * Adam(eps 1e-7) / SGD(momentum .9, wd 1e-4) (lightning_model.py:759-765) is one streaming kernel over the
     flat buffer that also emits the bf16 weight mirror for the next step's GEMMs.
 """
+import math
 import os
 
 import torch
@@ -45,7 +46,8 @@ def local_loss_count(model, batch):
 
 class NativeTrainer:
     def __init__(self, model, lr=1e-3, optimizer='Adam', process_group=None, token_weighted=False, grad_exchange_dtype='fp32',
-                 always_hook=False, exchange_schedule=None):
+                 always_hook=False, exchange_schedule=None, gradient_clip_val=None, gradient_clip_algorithm='norm',
+                 error_if_nonfinite=False):
         """model: a tagger from taggers.py / rnn_taggers.py (or a TextSegmenter, whose .model is used).
 
         token_weighted: the reference's loss is a mean over the LOCAL batch's valid sentences (models/CRF.py:352), so plain data
@@ -65,7 +67,21 @@ class NativeTrainer:
 
         always_hook: take the overlapped exchange path (gradient-ready hooks -> asynchronous all-reduce per span) even in a
         process group of ONE rank.  Measurement aid: the N > 1 step path -- hook order, per-projection release, collective
-        launches, stream waits -- on a single GPU (bench.py MTS_BENCH_SINGLE_RANK_DP=1); needs an initialised process group."""
+        launches, stream waits -- on a single GPU (bench.py MTS_BENCH_SINGLE_RANK_DP=1); needs an initialised process group.
+
+        gradient_clip_val / gradient_clip_algorithm: Lightning's Trainer arguments (train_fit.py:288,295,779 --gradient_clipping).
+        None or 0.0 = off: the step is the unclipped one, launch for launch.  'norm' = torch.nn.utils.clip_grad_norm_(max_norm =
+        gradient_clip_val) on the AVERAGED gradient (the 1/world of the optimizer is folded into the norm), 'value' =
+        clip_grad_value_.  The norm is reduced on the device inside apply_optimizer(), behind the exchange, over the spans the
+        optimizer steps; every rank reduces the same exchanged buffer in the same order and gets the same bits, so there is no
+        extra collective, and the optimizer kernel takes its coefficient from device memory: no host synchronisation.
+        After a 'norm' step `last_grad_norm` (the norm BEFORE clipping, what clip_grad_norm_ returns) and `last_clip_coef` (the
+        coefficient applied) are 0-d fp32 device tensors valid on the step's stream until the next step overwrites them; they
+        stay None when clipping is off or by value.  model.grad_flat() itself is left unscaled and unclipped.
+
+        error_if_nonfinite ('norm' only, as clip_grad_norm_): True reads the norm on the host (the one mode that synchronises) and
+        raises RuntimeError before the optimizer launch when it is NaN or Inf, leaving parameters, moments and step_count as they
+        were; False lets it propagate as torch does (coefficient NaN, parameters NaN)."""
         # a TextSegmenter wraps the tagger in .model; a bare tagger may itself own a parameter container called "model"
         self.model = model.model if hasattr(model, 'training_step') else model
         self.lr, self.kind = float(lr), optimizer
@@ -86,6 +102,16 @@ class NativeTrainer:
             raise ValueError("exchange_schedule must be 'allreduce' or 'rs_ag'")
         self.exchange_schedule = sched
         self._inflight_shards = []
+        if gradient_clip_algorithm not in ('norm', 'value'):
+            raise ValueError("gradient_clip_algorithm must be 'norm' or 'value'")
+        clip = float(gradient_clip_val) if gradient_clip_val is not None else 0.0
+        if not clip >= 0.0:
+            raise ValueError('gradient_clip_val must be >= 0 (None or 0.0: no clipping)')
+        self.gradient_clip_val = clip
+        self.clip_mode = gradient_clip_algorithm if clip > 0.0 else None
+        self.error_if_nonfinite = bool(error_if_nonfinite)
+        self.last_grad_norm = self.last_clip_coef = None
+        self._clip_stats = self._clip_ws = None
 
     def _state(self):
         flat = self.model.flat
@@ -237,20 +263,46 @@ class NativeTrainer:
                              f'min {int(-t[1].item())}): shard one collated batch with shard_batch() or pad to a common length')
         self._len_checked = Lq
 
+    def _grad_norm(self, spans, gscale):
+        """|| gscale * grad ||_2 over `spans`, left in device memory for the clipped optimizer kernel (-> last_grad_norm)."""
+        g = self.model.grad_flat()
+        if self._clip_stats is None or self._clip_stats.device != g.device:
+            self._clip_stats = torch.zeros(2, dtype=torch.float32, device=g.device)     # {norm before clipping, coefficient}
+            self._clip_ws = ops.grad_norm_workspace(g.device)
+            self.last_grad_norm, self.last_clip_coef = self._clip_stats[0], self._clip_stats[1]
+        ops.grad_norm(g, spans, gscale, self._clip_ws, self.last_grad_norm)
+        if self.error_if_nonfinite and not math.isfinite(float(self.last_grad_norm)):
+            raise RuntimeError(f'the total norm of the gradient is non-finite ({float(self.last_grad_norm)}), so it cannot be clipped '
+                               '(NativeTrainer(error_if_nonfinite=True))')
+
     def apply_optimizer(self):
         m = self.model
-        self.step_count += 1
         mirror = m._wcopy if (m.compute_dtype == torch.bfloat16 and m._wcopy is not None) else None
         gscale = 1.0 / self.world
+        g = m.grad_flat()
+        spans = [(0, m.flat.numel())] if self.kind == 'SGD' else self._adam_spans()
+        clip = {}
+        if self.clip_mode == 'norm':
+            self._grad_norm(spans, gscale)                # may raise (error_if_nonfinite): nothing has been stepped yet
+            clip = dict(total_norm=self.last_grad_norm, max_norm=self.gradient_clip_val, clip_coef_out=self.last_clip_coef)
+        elif self.clip_mode == 'value':
+            clip = dict(clip_value=self.gradient_clip_val)
+        self.step_count += 1
         if self.kind == 'SGD':
             buf, _ = self._state()
-            ops.sgd_step(m.flat, m.grad_flat(), buf, self.lr, 0.9, 1e-4, self.step_count == 1, gscale, mirror)
+            if clip:
+                ops.sgd_step_clipped(m.flat, g, buf, self.lr, 0.9, 1e-4, self.step_count == 1, gscale, mirror, **clip)
+            else:
+                ops.sgd_step(m.flat, g, buf, self.lr, 0.9, 1e-4, self.step_count == 1, gscale, mirror)
         else:
             mm, vv = self._state()
-            g = m.grad_flat()
-            for a, b in self._adam_spans():
-                ops.adam_step(m.flat[a:b], g[a:b], mm[a:b], vv[a:b], self.lr, 0.9, 0.999, 1e-7, self.step_count, gscale,
-                              mirror[a:b] if mirror is not None else None)
+            for a, b in spans:
+                args = (m.flat[a:b], g[a:b], mm[a:b], vv[a:b], self.lr, 0.9, 0.999, 1e-7, self.step_count, gscale,
+                        mirror[a:b] if mirror is not None else None)
+                if clip:
+                    ops.adam_step_clipped(*args, **clip)
+                else:
+                    ops.adam_step(*args)
         # the kernel wrote `flat` through a raw pointer, which does not bump torch's version counter: keep the
         # bf16-mirror cache of the model coherent by hand
         if mirror is not None:
