@@ -19,8 +19,8 @@
  *    mutable process-wide state that influences results or kernel choice: mts_last_error() and the tuning switches of
  *    mts_set_option() are PER HOST THREAD (a switch set by one thread applies to the calls that thread issues, and only
  *    those -- note that torch's autograd runs backward nodes on its own thread), mts_gemm_last_plan() reports the calling
- *    thread's most recent mts_gemm.  The only shared words are idempotent "function attribute already set" flags
- *    (atomics) and the sticky device-error word of mts_async_status();
+ *    thread's most recent mts_gemm.  The only shared words are the record of the dynamic-LDS limit already set per
+ *    (kernel, device) (atomics, appended under a mutex) and the sticky device-error word of mts_async_status();
  *  - "act dtype" = the arithmetic/storage type of activations: MTS_F32 (parity mode, fp32 everywhere) or
  *    MTS_BF16 (bf16 storage + MFMA, fp32 accumulate/statistics).  Parameters and gradients are always fp32.
  */

@@ -17,88 +17,10 @@
 //
 // Semantics (oracle/restatement.py::band_attention; modeling_longformer.py:482-640): key j = i - radius + c
 // takes part iff 0 <= j < len_b; a query i >= len_b yields a zero row.
-#include <algorithm>
-#include "band_common.h"
+#include "attn_tile.h"
 
 #define TQ 32
 #define KV_ROWS (TQ + 31)
-
-// ---- staging: rows [first, first+nrows) of one head's slice of a [B*L, ld] matrix into LDS; rows outside [0,L) -> 0
-template <typename T>
-__device__ __forceinline__ void stage_rows(char* dst, int rs, const T* __restrict__ doc_base, int ld, int first, int nrows, int L, int hd) {
-  constexpr int VEC = 16 / sizeof(T);
-  const int cpr = hd / VEC;                      // 16-byte chunks per row
-  for (int idx = threadIdx.x; idx < nrows * cpr; idx += 256) {
-    const int r = idx / cpr, ch = idx % cpr;
-    const int j = first + r;
-    uint4 v = make_uint4(0, 0, 0, 0);
-    if (j >= 0 && j < L) v = *reinterpret_cast<const uint4*>(doc_base + (size_t)j * ld + ch * VEC);
-    *reinterpret_cast<uint4*>(dst + r * rs + ch * 16) = v;
-  }
-}
-
-__device__ __forceinline__ float dot16(const uint4& a, const uint4& b, float acc, float) {   // 4 fp32 pairs
-  acc = fmaf(__uint_as_float(a.x), __uint_as_float(b.x), acc);
-  acc = fmaf(__uint_as_float(a.y), __uint_as_float(b.y), acc);
-  acc = fmaf(__uint_as_float(a.z), __uint_as_float(b.z), acc);
-  acc = fmaf(__uint_as_float(a.w), __uint_as_float(b.w), acc);
-  return acc;
-}
-__device__ __forceinline__ float dot16(const uint4& a, const uint4& b, float acc, bf16_t) {  // 8 bf16 pairs
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, a.x), __builtin_bit_cast(bf16x2, b.x), acc, false);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, a.y), __builtin_bit_cast(bf16x2, b.y), acc, false);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, a.z), __builtin_bit_cast(bf16x2, b.z), acc, false);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, a.w), __builtin_bit_cast(bf16x2, b.w), acc, false);
-  return acc;
-}
-
-// s[t] = <A[tq,:], Brows[tq + g + 8t,:]>, t = 0..3
-template <typename T>
-__device__ __forceinline__ void score_phase(const char* As, const char* Bs, int rs, int hd, int tq, int g, float (&s)[4]) {
-  constexpr int VEC = 16 / sizeof(T);
-  const int cpr = hd / VEC;
-  const char* a = As + tq * rs;
-  const char* b0 = Bs + (tq + g) * rs;
-  s[0] = s[1] = s[2] = s[3] = 0.f;
-  for (int ch = 0; ch < cpr; ++ch) {
-    const uint4 av = *reinterpret_cast<const uint4*>(a + ch * 16);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const uint4 bv = *reinterpret_cast<const uint4*>(b0 + (8 * t) * rs + ch * 16);
-      s[t] = dot16(av, bv, s[t], T());
-    }
-  }
-}
-
-// acc[uu][0..3] += sum_{cc<ncc} coef[cc] * Rows[row0 + cc][4*(dg + 8*uu) ..]
-template <typename T, int MAXU>
-__device__ __forceinline__ void accum_phase(const float* coef, int coef_stride, const char* Rows, int rs, int hd, int row0, int dg, int ncc,
-                                            float (&acc)[MAXU][4]) {
-  const int nch = hd / 4;
-  for (int cc = 0; cc < ncc; ++cc) {
-    const float p = coef[cc * coef_stride];
-    const T* row = reinterpret_cast<const T*>(Rows + (row0 + cc) * rs);
-#pragma unroll
-    for (int uu = 0; uu < MAXU; ++uu) {
-      const int u = dg + 8 * uu;
-      if (u < nch) {
-        float v[4];
-        load4<T>(row + 4 * u, v);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[uu][j] = fmaf(p, v[j], acc[uu][j]);
-      }
-    }
-  }
-}
-
-__device__ __forceinline__ float oct_max(float v) {   // reduce over the 8 lanes that share a query
-  v = fmaxf(v, __shfl_xor(v, 1, 64)); v = fmaxf(v, __shfl_xor(v, 2, 64)); v = fmaxf(v, __shfl_xor(v, 4, 64));
-  return v;
-}
-__device__ __forceinline__ float oct_sum(float v) {
-  v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64);
-  return v;
-}
 
 // ------------------------------------------------------------------------------------------------
 // forward
@@ -122,13 +44,13 @@ __global__ __launch_bounds__(256) void band_fwd_kernel(const BandArgs a) {
   const T* qbase = reinterpret_cast<const T*>(a.qkv) + (size_t)doc.base * ld + h * hd;
   const int nsb = a.slots / 32;
 
-  stage_rows<T>(Qs, a.rs, qbase, ld, i0, TQ, doc.Lb, hd);
+  attn_stage_rows<T>(Qs, a.rs, qbase, ld, i0, TQ, doc.Lb, hd);
   for (int sb = 0; sb < nsb; ++sb) {
     __syncthreads();   // previous block's readers are done with KVs (and Qs is complete after the first pass)
-    stage_rows<T>(KVs, a.rs, qbase + a.D, ld, i0 - w + 32 * sb, KV_ROWS, doc.Lb, hd);
+    attn_stage_rows<T>(KVs, a.rs, qbase + a.D, ld, i0 - w + 32 * sb, KV_ROWS, doc.Lb, hd);
     __syncthreads();
     float s[4];
-    score_phase<T>(Qs, KVs, a.rs, hd, tq, g, s);
+    attn_scores<T>(Qs + tq * a.rs, KVs + (tq + g) * a.rs, a.rs, hd, s);
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       const int c = 32 * sb + g + 8 * t;
@@ -143,14 +65,14 @@ __global__ __launch_bounds__(256) void band_fwd_kernel(const BandArgs a) {
     const bool qok = (i < len);
     float m = -INFINITY;
     for (int c = g; c < a.slots; c += 8) m = fmaxf(m, Ps[tq * a.ps + c]);
-    m = oct_max(m);
+    m = lanes8_max(m);
     float sum = 0.f;
     for (int c = g; c < a.slots; c += 8) {
       const float e = qok ? __expf(Ps[tq * a.ps + c] - m) : 0.f;   // exp(-inf) = 0 for masked keys
       Ps[tq * a.ps + c] = e;
       sum += e;
     }
-    sum = oct_sum(sum);
+    sum = lanes8_sum(sum);
     const float inv = qok ? 1.0f / sum : 0.f;
     float* prow = a.probs + ((size_t)(doc.base + i) * a.heads + h) * a.slots;
     for (int c = g; c < a.slots; c += 8) {
@@ -165,10 +87,10 @@ __global__ __launch_bounds__(256) void band_fwd_kernel(const BandArgs a) {
   for (int uu = 0; uu < MAXU; ++uu) acc[uu][0] = acc[uu][1] = acc[uu][2] = acc[uu][3] = 0.f;
   for (int sb = 0; sb < nsb; ++sb) {
     __syncthreads();
-    stage_rows<T>(KVs, a.rs, qbase + 2 * a.D, ld, i0 - w + 32 * sb, KV_ROWS, doc.Lb, hd);
+    attn_stage_rows<T>(KVs, a.rs, qbase + 2 * a.D, ld, i0 - w + 32 * sb, KV_ROWS, doc.Lb, hd);
     __syncthreads();
     const int ncc = min(32, W - 32 * sb);
-    accum_phase<T, MAXU>(Ps + tq * a.ps + 32 * sb, 1, KVs, a.rs, hd, tq, g, ncc, acc);
+    attn_accum<T, MAXU>(Ps + tq * a.ps + 32 * sb, 1, KVs + tq * a.rs, a.rs, hd, g, ncc, acc);
   }
   if (i < doc.Lb) {
     T* o = reinterpret_cast<T*>(a.ctx) + (size_t)(doc.base + i) * a.D + h * hd;
@@ -205,14 +127,14 @@ __global__ __launch_bounds__(256) void band_bwd_q_kernel(const BandArgs a) {
   const size_t prow_off = ((size_t)(doc.base + min(i, doc.Lb - 1)) * a.heads + h) * a.slots;
   const float* prow = a.probs + prow_off;
 
-  stage_rows<T>(Qs, a.rs, dcbase, a.D, i0, TQ, doc.Lb, hd);
+  attn_stage_rows<T>(Qs, a.rs, dcbase, a.D, i0, TQ, doc.Lb, hd);
   float delta = 0.f;
   for (int sb = 0; sb < nsb; ++sb) {
     __syncthreads();
-    stage_rows<T>(KVs, a.rs, qbase + 2 * a.D, ld, i0 - w + 32 * sb, KV_ROWS, doc.Lb, hd);   // V rows
+    attn_stage_rows<T>(KVs, a.rs, qbase + 2 * a.D, ld, i0 - w + 32 * sb, KV_ROWS, doc.Lb, hd);   // V rows
     __syncthreads();
     float s[4];
-    score_phase<T>(Qs, KVs, a.rs, hd, tq, g, s);     // dP
+    attn_scores<T>(Qs + tq * a.rs, KVs + (tq + g) * a.rs, a.rs, hd, s);     // dP
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       const int c = 32 * sb + g + 8 * t;
@@ -222,7 +144,7 @@ __global__ __launch_bounds__(256) void band_bwd_q_kernel(const BandArgs a) {
       delta += p * s[t];
     }
   }
-  delta = oct_sum(delta);
+  delta = lanes8_sum(delta);
   __syncthreads();
   {
     float* dsrow = a.dscores + prow_off;
@@ -238,10 +160,10 @@ __global__ __launch_bounds__(256) void band_bwd_q_kernel(const BandArgs a) {
   for (int uu = 0; uu < MAXU; ++uu) acc[uu][0] = acc[uu][1] = acc[uu][2] = acc[uu][3] = 0.f;
   for (int sb = 0; sb < nsb; ++sb) {
     __syncthreads();
-    stage_rows<T>(KVs, a.rs, qbase + a.D, ld, i0 - w + 32 * sb, KV_ROWS, doc.Lb, hd);       // K rows
+    attn_stage_rows<T>(KVs, a.rs, qbase + a.D, ld, i0 - w + 32 * sb, KV_ROWS, doc.Lb, hd);       // K rows
     __syncthreads();
     const int ncc = min(32, W - 32 * sb);
-    accum_phase<T, MAXU>(Ps + tq * a.ps + 32 * sb, 1, KVs, a.rs, hd, tq, g, ncc, acc);
+    attn_accum<T, MAXU>(Ps + tq * a.ps + 32 * sb, 1, KVs + tq * a.rs, a.rs, hd, g, ncc, acc);
   }
   if (i < doc.Lb) {
     T* o = reinterpret_cast<T*>(a.dqkv) + (size_t)(doc.base + i) * ld + h * hd;
@@ -279,7 +201,7 @@ __global__ __launch_bounds__(256) void band_bwd_kv_kernel(const BandArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* Rs = smem;                                               // KV_ROWS rows of q (or dCtx)
   float* raw = reinterpret_cast<float*>(Rs + KV_ROWS * a.rs);    // [KV_ROWS][32]
-  float* PT = raw + KV_ROWS * 32;                                // [TQ][33]
+  float* PT = raw + KV_ROWS * 32;                                // [TQ][PS]
 
   const int ntiles = (a.L + TQ - 1) / TQ;
   int tile, h, b;
@@ -309,13 +231,13 @@ __global__ __launch_bounds__(256) void band_bwd_kv_kernel(const BandArgs a) {
     for (int pass = 0; pass < 2; ++pass) {
       __syncthreads();
       stage_coef(raw, pass == 0 ? dsb : pb, xrow, first_i, doc.Lb, cbase, W, a, doc.base, h, pass == 1 && a.drop_thr != 0);
-      if (pass == 0) stage_rows<T>(Rs, a.rs, qbase, ld, first_i, KV_ROWS, doc.Lb, hd);          // scaled q rows
-      else stage_rows<T>(Rs, a.rs, dcbase, a.D, first_i, KV_ROWS, doc.Lb, hd);                  // dCtx rows
+      if (pass == 0) attn_stage_rows<T>(Rs, a.rs, qbase, ld, first_i, KV_ROWS, doc.Lb, hd);          // scaled q rows
+      else attn_stage_rows<T>(Rs, a.rs, dcbase, a.D, first_i, KV_ROWS, doc.Lb, hd);                  // dCtx rows
       __syncthreads();
-      for (int cc = g; cc < 32; cc += 8) PT[tk * 33 + cc] = raw[(tk + cc) * 32 + (31 - cc)];
+      for (int cc = g; cc < 32; cc += 8) PT[tk * PS + cc] = raw[(tk + cc) * 32 + (31 - cc)];
       __syncthreads();
-      if (pass == 0) accum_phase<T, MAXU>(PT + tk * 33, 1, Rs, a.rs, hd, tk, g, ncc, dk);
-      else accum_phase<T, MAXU>(PT + tk * 33, 1, Rs, a.rs, hd, tk, g, ncc, dv);
+      if (pass == 0) attn_accum<T, MAXU>(PT + tk * PS, 1, Rs + tk * a.rs, a.rs, hd, g, ncc, dk);
+      else attn_accum<T, MAXU>(PT + tk * PS, 1, Rs + tk * a.rs, a.rs, hd, g, ncc, dv);
     }
   }
   if (j < doc.Lb) {
@@ -337,12 +259,6 @@ void mts_band_set_mfma(int on) { g_band_mfma = on; }
 
 extern "C" int mts_band_slots(int radius) { return band_slots(radius); }
 
-static int band_row_stride(int hd, int esize) {
-  int bytes = ((hd * esize + 15) / 16) * 16;
-  if (((bytes / 16) & 1) == 0) bytes += 16;   // stride = 16 B x odd: 16 rows at one column hit 16 distinct 16-byte bank slots
-  return bytes;
-}
-
 static int band_fill(BandArgs& a, int dtype, int B, int L, int D, int heads, int radius, const char* who) {
   MTS_CHECK_ARG(B > 0 && L > 0 && D > 0 && heads > 0 && radius > 0, "%s: bad shape", who);
   MTS_CHECK_ARG(D % heads == 0, "%s: D=%d not divisible by heads=%d", who, D, heads);
@@ -352,7 +268,7 @@ static int band_fill(BandArgs& a, int dtype, int B, int L, int D, int heads, int
   MTS_UNSUPPORTED(hd % vec == 0 && hd <= 512, "%s: head dim %d must be a multiple of %d and <= 512", who, hd, vec);
   MTS_UNSUPPORTED((long)B * L * heads * (long)band_slots(radius) < (1L << 31), "%s: problem too large for 32-bit slot indexing", who);
   a.B = B; a.L = L; a.D = D; a.heads = heads; a.hd = hd; a.radius = radius; a.slots = band_slots(radius);
-  a.rs = band_row_stride(hd, dtype == MTS_F32 ? 4 : 2);
+  a.rs = attn_row_stride(hd, dtype == MTS_F32 ? 4 : 2);
   a.ps = a.slots + 1;
   a.q_scale = 1.f;
   a.bias_slab = nullptr; a.img_bytes = 0; a.row0 = nullptr;
@@ -361,31 +277,12 @@ static int band_fill(BandArgs& a, int dtype, int B, int L, int D, int heads, int
   return MTS_OK;
 }
 
-static int band_set_dropout(BandArgs& a, float p, uint64_t seed, const char* who) {
-  MTS_CHECK_ARG(p >= 0.f && p < 1.f, "%s: dropout probability has to be between 0 and 1, but got %f", who, (double)p);
-  if (p > 0.f) {
-    a.drop_thr = (uint32_t)std::max<double>(1.0, std::min<double>(4294967295.0, (double)p * 4294967296.0));
-    a.drop_scale = 1.0f / (1.0f - p);
-    a.drop_seed = seed;
-  }
-  return MTS_OK;
-}
-
-template <typename K> static int set_lds(K kernel, size_t bytes, const char* who) {
-  MTS_UNSUPPORTED(bytes <= 160 * 1024, "%s: needs %zu bytes of LDS (> 160 KiB): window too wide for this head dim", who, bytes);
-  if (bytes > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) { mts_set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e)); return MTS_ERR_LAUNCH; }
-  }
-  return MTS_OK;
-}
-
 template <typename T>
 static int band_fwd_launch(const BandArgs& a, hipStream_t st) {
   const size_t lds = (size_t)(TQ + KV_ROWS) * a.rs + (size_t)TQ * a.ps * sizeof(float);
   const int nblocks = ceil_div(a.L, TQ) * a.heads * a.B;
   auto k = a.hd > 256 ? band_fwd_kernel<T, 16> : band_fwd_kernel<T, 8>;       // 8 lanes x MAXU chunks of 4 cover the head dim
-  int rc = set_lds(k, lds, "mts_band_attn_fwd");
+  int rc = mts_dyn_lds(k, lds, "mts_band_attn_fwd");
   if (rc) return rc;
   hipLaunchKernelGGL(k, dim3(nblocks), dim3(256), lds, st, a);
   MTS_LAUNCH_CHECK("mts_band_attn_fwd");
@@ -400,7 +297,7 @@ extern "C" int mts_band_attn_fwd(void* stream, int dtype, int B, int L, int D, i
   MTS_CHECK_ARG(qkv && ctx && probs, "mts_band_attn_fwd: null pointer");
   MTS_CHECK_ARG(!row0 || lengths, "mts_band_attn_fwd: packed rows (row0) need lengths");
   a.row0 = row0;
-  rc = band_set_dropout(a, drop_p, drop_seed, "mts_band_attn_fwd");
+  rc = attn_set_dropout(a, drop_p, drop_seed, "mts_band_attn_fwd");
   if (rc) return rc;
   a.qkv = qkv; a.lengths = lengths; a.ctx = ctx; a.probs = probs;
   if (dtype == MTS_BF16 && g_band_mfma) {
@@ -416,14 +313,14 @@ static int band_bwd_launch(const BandArgs& a, hipStream_t st) {
   {
     const size_t lds = (size_t)(TQ + KV_ROWS) * a.rs + (size_t)TQ * a.ps * sizeof(float);
     auto k = a.hd > 256 ? band_bwd_q_kernel<T, 16> : band_bwd_q_kernel<T, 8>;
-    int rc = set_lds(k, lds, "mts_band_attn_bwd(q)");
+    int rc = mts_dyn_lds(k, lds, "mts_band_attn_bwd(q)");
     if (rc) return rc;
     hipLaunchKernelGGL(k, dim3(nblocks), dim3(256), lds, st, a);
   }
   {
-    const size_t lds = (size_t)KV_ROWS * a.rs + (size_t)(KV_ROWS * 32 + TQ * 33) * sizeof(float);
+    const size_t lds = (size_t)KV_ROWS * a.rs + (size_t)(KV_ROWS * 32 + TQ * PS) * sizeof(float);
     auto k = a.hd > 256 ? band_bwd_kv_kernel<T, 16> : band_bwd_kv_kernel<T, 8>;
-    int rc = set_lds(k, lds, "mts_band_attn_bwd(kv)");
+    int rc = mts_dyn_lds(k, lds, "mts_band_attn_bwd(kv)");
     if (rc) return rc;
     hipLaunchKernelGGL(k, dim3(nblocks), dim3(256), lds, st, a);
   }
@@ -449,7 +346,7 @@ extern "C" int mts_band_attn_bwd(void* stream, int dtype, int B, int L, int D, i
   MTS_CHECK_ARG(!dbias || workspace, "mts_band_attn_bwd: dbias needs mts_band_attn_bwd_workspace() bytes of workspace");
   MTS_CHECK_ARG(!row0 || (lengths && n_rows > 0 && n_rows <= B * L), "mts_band_attn_bwd: packed rows (row0) need lengths and 0 < n_rows <= B*L");
   a.row0 = row0;
-  rc = band_set_dropout(a, drop_p, drop_seed, "mts_band_attn_bwd");
+  rc = attn_set_dropout(a, drop_p, drop_seed, "mts_band_attn_bwd");
   if (rc) return rc;
   a.qkv = qkv; a.lengths = lengths; a.probs = const_cast<float*>(probs); a.dctx = dctx; a.dqkv = dqkv; a.dscores = dscores;
   a.q_scale = q_scale;

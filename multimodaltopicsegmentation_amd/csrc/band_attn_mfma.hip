@@ -754,10 +754,7 @@ static int launch(K kernel, BandArgs a, int nkb, hipStream_t st, const char* who
   const int nrows = TROWS - WROWS + 16 * nkb;
   a.img_bytes = (int)align_up((size_t)nrows * a.hd * 2, (size_t)1024);      // whole 1-KiB DMA pieces
   const size_t lds = (size_t)a.img_bytes + 4 * (size_t)a.hd * sizeof(float);  // + the 4 waves' column sums
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { mts_set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e)); return MTS_ERR_LAUNCH; }
-  }
+  if (int rc = mts_dyn_lds(kernel, lds, who)) return rc;
   const int nblocks = ceil_div(a.L, TROWS) * a.heads * a.B;
   hipLaunchKernelGGL(kernel, dim3(nblocks), dim3(256), lds, st, a);
   MTS_LAUNCH_CHECK(who);
@@ -819,12 +816,7 @@ template <int KK>
 static int launch_fused(const BandArgs& a, hipStream_t st, int* slab_rows) {
   auto k = band_mfma_bwd_fused_kernel<KK>;
   const size_t lds = FusedLds<KK>::TOTAL;
-  static std::atomic<bool> attr{false};
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { mts_set_error("mts_band_attn_bwd(fused): hipFuncSetAttribute: %s", hipGetErrorString(e)); return MTS_ERR_LAUNCH; }
-    attr = true;
-  }
+  if (int rc = mts_dyn_lds(k, lds, "mts_band_attn_bwd(fused)")) return rc;
   const int halo = a.L <= FROWS ? 0 : 16, tk = FROWS - (halo ? 64 : 0);      // 256 rows, or 192 key rows inside 224 query rows
   const int ntiles = ceil_div(a.L, tk);
   hipLaunchKernelGGL(k, dim3(ntiles * a.heads * a.B), dim3(512), lds, st, a, tk, halo, ntiles);

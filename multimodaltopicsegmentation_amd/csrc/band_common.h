@@ -1,5 +1,6 @@
-// Shared by the two band-attention translation units (band_attn.hip: generic VALU kernels, fp32/bf16, any head dim;
-// band_attn_mfma.hip: bf16 matrix-core kernels for head dims that are multiples of 32).
+// Shared by the attention translation units: BandArgs and the dropout keep rule of the two band-attention ones (band_attn.hip:
+// generic VALU kernels, fp32/bf16, any head dim; band_attn_mfma.hip: bf16 matrix-core kernels for head dims that are multiples
+// of 32), and the block decode that every attention kernel uses.
 #pragma once
 #include "common.h"
 
@@ -20,14 +21,11 @@ __host__ __device__ inline int band_slots(int radius) { return ((2 * radius + 1 
 
 // decode the XCD-remapped linear block id into (tile, head, doc): consecutive tiles of one (doc, head) stay on one XCD
 __device__ __forceinline__ void decode_block(int ntiles, int heads, int nblocks, int& tile, int& h, int& b) {
-  int bid = blockIdx.x;
-  const int q = nblocks >> 3, rr = nblocks & 7, xcd = bid & 7, idx = bid >> 3;
-  bid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + idx;
+  const int bid = xcd_remap(blockIdx.x, nblocks);
   tile = bid % ntiles;
   h = (bid / ntiles) % heads;
   b = bid / (ntiles * heads);
 }
-
 
 // where document b lives: first row and number of rows that exist for it
 struct DocView { int base; int Lb; };

@@ -42,6 +42,14 @@ void mts_set_error(const char* fmt, ...);
     }                                                                                 \
   } while (0)
 
+// Dynamic LDS above the 64 KiB every kernel may use: opts `kernel` in for at least `bytes` on the calling thread's current device
+// (the limit is a property of (kernel, device)) unless that is remembered as done, so a steady-state launch makes no runtime call.
+// MTS_ERR_UNSUPPORTED above the CU's 160 KiB.  Defined in optim.hip.
+int mts_dyn_lds(const void* kernel, size_t bytes, const char* who);
+template <typename K> static inline int mts_dyn_lds(K* kernel, size_t bytes, const char* who) {
+  return mts_dyn_lds(reinterpret_cast<const void*>(kernel), bytes, who);
+}
+
 // ---- scalar conversions -----------------------------------------------------------------------
 __device__ __forceinline__ float to_f32(float v) { return v; }
 __device__ __forceinline__ float to_f32(bf16_t v) { return (float)v; }
@@ -136,6 +144,13 @@ __host__ __device__ inline uint32_t mts_hash32(uint64_t seed, uint64_t idx) {   
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   z = z ^ (z >> 31);
   return (uint32_t)(z >> 32);
+}
+
+// XCD remap of a linear block id: workgroups id, id + 8, .. run on one XCD (own L2), so XCD x takes a contiguous run of the n work
+// items and its workgroups walk it in order
+__host__ __device__ __forceinline__ int xcd_remap(int id, int n) {
+  const int q = n >> 3, rr = n & 7, xcd = id & 7, idx = id >> 3;
+  return (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + idx;
 }
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }

@@ -362,13 +362,7 @@ extern "C" int mts_crf_viterbi(void* stream, int B, int L, int C, const float* f
   MTS_CHECK_ARG(feats && trans && best_score && paths && bp_ws, "mts_crf_viterbi: null pointer");
   const size_t bp_bytes = (size_t)16 * L;                   // one byte per document and step (four 2-bit back-pointers)
   bool quad = C == 4 && bp_bytes <= 160 * 1024;
-  if (quad && bp_bytes > 64 * 1024) {
-    static std::atomic<bool> attr{false};
-    if (!attr) {
-      if (hipFuncSetAttribute((const void*)crf_viterbi4_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) quad = false;
-      else attr = true;
-    }
-  }
+  if (quad && mts_dyn_lds(crf_viterbi4_kernel, bp_bytes, "mts_crf_viterbi") != MTS_OK) quad = false;
   if (quad)
     hipLaunchKernelGGL(crf_viterbi4_kernel, dim3(ceil_div(B, 16)), dim3(64), bp_bytes, (hipStream_t)stream, B, L, feats, lengths, trans, best_score,
                        paths);

@@ -383,13 +383,11 @@ static int ffn_launch(bool bwd, hipStream_t st, const FfnArgs& a0) {
   const int grid = ceil_div(a.M, FF_BM);
   if (bwd) {
     auto k = ffn_fused_kernel<true>;
-    static std::atomic<bool> attr{false};
-    if (!attr) { if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, FF_LDS) != hipSuccess) { mts_set_error("ffn_fused: cannot reserve %d bytes of LDS", FF_LDS); return MTS_ERR_LAUNCH; } attr = true; }
+    if (int rc = mts_dyn_lds(k, FF_LDS, "ffn_fused")) return rc;
     hipLaunchKernelGGL(k, dim3(grid), dim3(FF_THREADS), FF_LDS, st, a);
   } else {
     auto k = ffn_fused_kernel<false>;
-    static std::atomic<bool> attr{false};
-    if (!attr) { if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, FF_LDS) != hipSuccess) { mts_set_error("ffn_fused: cannot reserve %d bytes of LDS", FF_LDS); return MTS_ERR_LAUNCH; } attr = true; }
+    if (int rc = mts_dyn_lds(k, FF_LDS, "ffn_fused")) return rc;
     hipLaunchKernelGGL(k, dim3(grid), dim3(FF_THREADS), FF_LDS, st, a);
   }
   MTS_LAUNCH_CHECK("mts_ffn_fused");

@@ -5,7 +5,7 @@
 // at or past len_b are never visited), q pre-scaled by 1/sqrt(hd).  Padded query rows are NOT zeroed (BERT has no such step):
 // on the padded [B, L] layout they attend to the document's valid keys like any other row.
 //
-// Work decomposition (the band kernels' lane layout, band_attn.hip): one 256-thread workgroup per (document, head, tile of 32
+// Work decomposition (the lane layout and helpers of attn_tile.h): one 256-thread workgroup per (document, head, tile of 32
 // rows); lane = (row t = tid/8, group g = tid%8).  Score-type products <A[t], B[g + 8c]>, c = 0..3, are 16-byte LDS dot products
 // (v_dot2_f32_bf16 on bf16 pairs); accumulations over 32 coefficients stream 4-element chunks g + 8u of the head dim.
 //
@@ -16,10 +16,7 @@
 //   backward kv : per KEY tile; per query tile the same P and dS, transposed through LDS; dV += P_dropped^T dCtx, dK += dS^T Q.
 // Two kernels, fixed loop orders, no atomics: bitwise reproducible.  Nothing N x N ever touches memory.
 // bf16 at head dims that are multiples of 32 (<= 256) takes the matrix-core kernels further down instead (option "full_mfma").
-#include <algorithm>
-#include <mutex>
-#include <vector>
-#include "band_common.h"
+#include "attn_tile.h"
 
 #define FT 32   // rows per tile (queries and keys)
 
@@ -45,84 +42,6 @@ __device__ __forceinline__ bool full_keep(const FullArgs& a, int grow, int h, in
   return mts_hash32(a.drop_seed, ((uint64_t)grow * a.heads + h) * (uint64_t)a.L + (uint64_t)j) >= a.drop_thr;
 }
 
-// rows [first, first + FT) of one head's slice of a row-major [., ld] matrix into LDS; rows at or past `limit` -> 0
-template <typename T>
-__device__ __forceinline__ void full_stage(char* dst, int rs, const T* __restrict__ base, int ld, int first, int limit, int hd) {
-  constexpr int VEC = 16 / sizeof(T);
-  const int cpr = hd / VEC;
-  for (int idx = threadIdx.x; idx < FT * cpr; idx += 256) {
-    const int r = idx / cpr, ch = idx % cpr;
-    const int j = first + r;
-    uint4 v = make_uint4(0, 0, 0, 0);
-    if (j < limit) v = *reinterpret_cast<const uint4*>(base + (size_t)j * ld + ch * VEC);
-    *reinterpret_cast<uint4*>(dst + r * rs + ch * 16) = v;
-  }
-}
-
-__device__ __forceinline__ float fdot16(const uint4& a, const uint4& b, float acc, float) {
-  acc = fmaf(__uint_as_float(a.x), __uint_as_float(b.x), acc);
-  acc = fmaf(__uint_as_float(a.y), __uint_as_float(b.y), acc);
-  acc = fmaf(__uint_as_float(a.z), __uint_as_float(b.z), acc);
-  acc = fmaf(__uint_as_float(a.w), __uint_as_float(b.w), acc);
-  return acc;
-}
-__device__ __forceinline__ float fdot16(const uint4& a, const uint4& b, float acc, bf16_t) {
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, a.x), __builtin_bit_cast(bf16x2, b.x), acc, false);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, a.y), __builtin_bit_cast(bf16x2, b.y), acc, false);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, a.z), __builtin_bit_cast(bf16x2, b.z), acc, false);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, a.w), __builtin_bit_cast(bf16x2, b.w), acc, false);
-  return acc;
-}
-
-// s[c] = <A[t, :], B[g + 8c, :]>, c = 0..3
-template <typename T>
-__device__ __forceinline__ void full_scores(const char* As, const char* Bs, int rs, int hd, int t, int g, float (&s)[4]) {
-  constexpr int VEC = 16 / sizeof(T);
-  const int cpr = hd / VEC;
-  const char* ar = As + t * rs;
-  const char* br = Bs + g * rs;
-  s[0] = s[1] = s[2] = s[3] = 0.f;
-  for (int ch = 0; ch < cpr; ++ch) {
-    const uint4 av = *reinterpret_cast<const uint4*>(ar + ch * 16);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const uint4 bv = *reinterpret_cast<const uint4*>(br + (8 * c) * rs + ch * 16);
-      s[c] = fdot16(av, bv, s[c], T());
-    }
-  }
-}
-
-// acc[u][0..3] += sum_{c < ncc} coef[c] * Rows[c][4*(g + 8u) ..]
-template <typename T, int MAXU>
-__device__ __forceinline__ void full_accum(const float* coef, const char* Rows, int rs, int hd, int g, int ncc, float (&acc)[MAXU][4]) {
-  const int nch = hd / 4;
-  for (int c = 0; c < ncc; ++c) {
-    const float p = coef[c];
-    const T* row = reinterpret_cast<const T*>(Rows + c * rs);
-#pragma unroll
-    for (int u = 0; u < MAXU; ++u) {
-      const int ch = g + 8 * u;
-      if (ch < nch) {
-        float v[4];
-        load4<T>(row + 4 * ch, v);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[u][e] = fmaf(p, v[e], acc[u][e]);
-      }
-    }
-  }
-}
-
-__device__ __forceinline__ float f8_max(float v) {   // over the 8 lanes of one row
-  v = fmaxf(v, __shfl_xor(v, 1, 64)); v = fmaxf(v, __shfl_xor(v, 2, 64)); v = fmaxf(v, __shfl_xor(v, 4, 64));
-  return v;
-}
-__device__ __forceinline__ float f8_sum(float v) {
-  v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64);
-  return v;
-}
-
-#define PS (FT + 1)   // LDS row stride (floats) of a 32 x 32 coefficient tile
-
 // ------------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------------
@@ -144,7 +63,7 @@ __global__ __launch_bounds__(256) void full_fwd_kernel(const FullArgs a) {
   const int hd = a.hd, ld = 3 * a.D;
   const T* qbase = reinterpret_cast<const T*>(a.qkv) + (size_t)doc.base * ld + h * hd;
 
-  full_stage<T>(Qs, a.rs, qbase, ld, i0, doc.nrows, hd);
+  attn_stage_rows<T>(Qs, a.rs, qbase, ld, i0, FT, doc.nrows, hd);
   float m = -INFINITY, l = 0.f;
   float acc[MAXU][4];
 #pragma unroll
@@ -153,17 +72,17 @@ __global__ __launch_bounds__(256) void full_fwd_kernel(const FullArgs a) {
   for (int kt = 0; kt < nkt; ++kt) {
     const int j0 = kt * FT;
     __syncthreads();                                 // previous tile's readers are done with KVs
-    full_stage<T>(KVs, a.rs, qbase + a.D, ld, j0, doc.len, hd);
+    attn_stage_rows<T>(KVs, a.rs, qbase + a.D, ld, j0, FT, doc.len, hd);
     __syncthreads();
     float s[4];
-    full_scores<T>(Qs, KVs, a.rs, hd, t, g, s);
+    attn_scores<T>(Qs + t * a.rs, KVs + g * a.rs, a.rs, hd, s);
     float mt = -INFINITY;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       if (j0 + g + 8 * c >= doc.len) s[c] = -INFINITY;
       mt = fmaxf(mt, s[c]);
     }
-    const float mn = fmaxf(m, f8_max(mt));           // finite: key j0 < len is in every visited tile
+    const float mn = fmaxf(m, lanes8_max(mt));           // finite: key j0 < len is in every visited tile
     const float alpha = __expf(m - mn);              // 0 on the first tile (m = -inf)
     float ps = 0.f;
 #pragma unroll
@@ -173,16 +92,16 @@ __global__ __launch_bounds__(256) void full_fwd_kernel(const FullArgs a) {
       const int j = j0 + g + 8 * c;
       Ps[t * PS + g + 8 * c] = a.drop_thr ? (full_keep(a, doc.base + i, h, j) ? p * a.drop_scale : 0.f) : p;
     }
-    l = l * alpha + f8_sum(ps);
+    l = l * alpha + lanes8_sum(ps);
     m = mn;
 #pragma unroll
     for (int u = 0; u < MAXU; ++u)
 #pragma unroll
       for (int e = 0; e < 4; ++e) acc[u][e] *= alpha;
     __syncthreads();                                 // K scores done: KVs takes V
-    full_stage<T>(KVs, a.rs, qbase + 2 * a.D, ld, j0, doc.len, hd);
+    attn_stage_rows<T>(KVs, a.rs, qbase + 2 * a.D, ld, j0, FT, doc.len, hd);
     __syncthreads();
-    full_accum<T, MAXU>(Ps + t * PS, KVs, a.rs, hd, g, min(FT, doc.len - j0), acc);
+    attn_accum<T, MAXU>(Ps + t * PS, 1, KVs, a.rs, hd, g, min(FT, doc.len - j0), acc);
   }
   if (i < doc.nrows) {
     const float inv = 1.0f / l;
@@ -226,8 +145,8 @@ __global__ __launch_bounds__(256) void full_bwd_q_kernel(const FullArgs a) {
   const T* dobase = reinterpret_cast<const T*>(a.dctx) + (size_t)doc.base * a.D + h * hd;
   const T* obase = reinterpret_cast<const T*>(a.ctx) + (size_t)doc.base * a.D + h * hd;
 
-  full_stage<T>(Qs, a.rs, qbase, ld, i0, doc.nrows, hd);
-  full_stage<T>(dOs, a.rs, dobase, a.D, i0, doc.nrows, hd);
+  attn_stage_rows<T>(Qs, a.rs, qbase, ld, i0, FT, doc.nrows, hd);
+  attn_stage_rows<T>(dOs, a.rs, dobase, a.D, i0, FT, doc.nrows, hd);
   // delta_i = dCtx_i . ctx_i (= rowsum(P o dP) of the dropped probabilities: ctx is what they produced)
   float delta = 0.f;
   if (qok) {
@@ -243,7 +162,7 @@ __global__ __launch_bounds__(256) void full_bwd_q_kernel(const FullArgs a) {
       }
     }
   }
-  delta = f8_sum(delta);
+  delta = lanes8_sum(delta);
   const float lse = qok ? a.lse[(size_t)(doc.base + i) * a.heads + h] : INFINITY;
   if (qok && g == 0) a.delta[(size_t)(doc.base + i) * a.heads + h] = delta;
 
@@ -254,12 +173,12 @@ __global__ __launch_bounds__(256) void full_bwd_q_kernel(const FullArgs a) {
   for (int kt = 0; kt < nkt; ++kt) {
     const int j0 = kt * FT;
     __syncthreads();
-    full_stage<T>(Ks, a.rs, qbase + a.D, ld, j0, doc.len, hd);
-    full_stage<T>(Vs, a.rs, qbase + 2 * a.D, ld, j0, doc.len, hd);
+    attn_stage_rows<T>(Ks, a.rs, qbase + a.D, ld, j0, FT, doc.len, hd);
+    attn_stage_rows<T>(Vs, a.rs, qbase + 2 * a.D, ld, j0, FT, doc.len, hd);
     __syncthreads();
     float s[4], dp[4];
-    full_scores<T>(Qs, Ks, a.rs, hd, t, g, s);
-    full_scores<T>(dOs, Vs, a.rs, hd, t, g, dp);
+    attn_scores<T>(Qs + t * a.rs, Ks + g * a.rs, a.rs, hd, s);
+    attn_scores<T>(dOs + t * a.rs, Vs + g * a.rs, a.rs, hd, dp);
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       const int j = j0 + g + 8 * c;
@@ -269,7 +188,7 @@ __global__ __launch_bounds__(256) void full_bwd_q_kernel(const FullArgs a) {
       Ps[t * PS + g + 8 * c] = p * (d - delta);
     }
     __syncthreads();
-    full_accum<T, MAXU>(Ps + t * PS, Ks, a.rs, hd, g, min(FT, doc.len - j0), acc);
+    attn_accum<T, MAXU>(Ps + t * PS, 1, Ks, a.rs, hd, g, min(FT, doc.len - j0), acc);
   }
   if (qok) {
     T* o = reinterpret_cast<T*>(a.dqkv) + (size_t)(doc.base + i) * ld + h * hd;
@@ -318,14 +237,14 @@ __global__ __launch_bounds__(256) void full_bwd_kv_kernel(const FullArgs a) {
     for (int e = 0; e < 4; ++e) dk[u][e] = dv[u][e] = 0.f;
 
   if (j0 < doc.len) {                                 // padded keys (padded layout only): probability 0, gradient 0
-    full_stage<T>(Ks, a.rs, qbase + a.D, ld, j0, doc.len, hd);
-    full_stage<T>(Vs, a.rs, qbase + 2 * a.D, ld, j0, doc.len, hd);
+    attn_stage_rows<T>(Ks, a.rs, qbase + a.D, ld, j0, FT, doc.len, hd);
+    attn_stage_rows<T>(Vs, a.rs, qbase + 2 * a.D, ld, j0, FT, doc.len, hd);
     const int nqt = (doc.nrows + FT - 1) / FT;
     for (int qt = 0; qt < nqt; ++qt) {
       const int i0 = qt * FT;
       __syncthreads();
-      full_stage<T>(Qs, a.rs, qbase, ld, i0, doc.nrows, hd);
-      full_stage<T>(dOs, a.rs, dobase, a.D, i0, doc.nrows, hd);
+      attn_stage_rows<T>(Qs, a.rs, qbase, ld, i0, FT, doc.nrows, hd);
+      attn_stage_rows<T>(dOs, a.rs, dobase, a.D, i0, FT, doc.nrows, hd);
       if (threadIdx.x < FT) {
         const int i = i0 + threadIdx.x;
         const bool ok = i < doc.nrows;
@@ -334,8 +253,8 @@ __global__ __launch_bounds__(256) void full_bwd_kv_kernel(const FullArgs a) {
       }
       __syncthreads();
       float s[4], dp[4];
-      full_scores<T>(Ks, Qs, a.rs, hd, t, g, s);
-      full_scores<T>(Vs, dOs, a.rs, hd, t, g, dp);
+      attn_scores<T>(Ks + t * a.rs, Qs + g * a.rs, a.rs, hd, s);
+      attn_scores<T>(Vs + t * a.rs, dOs + g * a.rs, a.rs, hd, dp);
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         const int ci = g + 8 * c, i = i0 + ci;
@@ -347,8 +266,8 @@ __global__ __launch_bounds__(256) void full_bwd_kv_kernel(const FullArgs a) {
       }
       __syncthreads();
       const int ncq = min(FT, doc.nrows - i0);
-      full_accum<T, MAXU>(PT + t * PS, dOs, a.rs, hd, g, ncq, dv);
-      full_accum<T, MAXU>(ST + t * PS, Qs, a.rs, hd, g, ncq, dk);
+      attn_accum<T, MAXU>(PT + t * PS, 1, dOs, a.rs, hd, g, ncq, dv);
+      attn_accum<T, MAXU>(ST + t * PS, 1, Qs, a.rs, hd, g, ncq, dk);
     }
   }
   if (j < doc.nrows) {
@@ -364,9 +283,7 @@ __global__ __launch_bounds__(256) void full_bwd_kv_kernel(const FullArgs a) {
 // ------------------------------------------------------------------------------------------------
 // bf16 matrix-core path (head dim a multiple of 32, <= 256): v_mfma_f32_16x16x32_bf16, 4 waves x 16 rows per workgroup.
 //
-// Every product is written as X . Y^T with X and Y row-major LDS images whose rows run along the summed index: lane l takes
-// X[row l&15][8(l>>4) .. +7] as the A fragment and Y[row l&15][8(l>>4) .. +7] as the B fragment of one 32-wide k-step, and
-// the 16 x 16 result sits at C[row 4(l>>4) + r][col l&15], r = 0..3.  Products that sum over keys (P V, dS K) or over queries
+// Every product is X . Y^T in the fragment layout of attn_tile.h.  Products that sum over keys (P V, dS K) or over queries
 // (P^T dO, dS^T Q) read transposed images ([dim][key] / [dim][query]) written while staging, and P / dS cross LDS once per wave
 // to become A fragments.  Same tiles and loop orders on every run, no atomics: bitwise reproducible.
 //
@@ -375,62 +292,6 @@ __global__ __launch_bounds__(256) void full_bwd_kv_kernel(const FullArgs a) {
 //   dq      : workgroup = 64 queries; per 32-key tile S = Q K^T, dP = dO V^T, dS = P (dP - delta) (bf16) -> LDS, dQ += dS Kt^T.
 //   dk / dv : workgroup = 64 keys; per 32-query tile S^T = K Q^T, dP^T = V dO^T, dV += P^T dOt^T, dK += dS^T Qt^T.
 // ------------------------------------------------------------------------------------------------
-#define MQ 64                 // rows per workgroup
-#define MK 32                 // columns per step
-#define TRS (MK * 2 + 16)     // bytes per row of a transposed [dim][32] image (16-byte aligned, padded)
-
-__device__ __forceinline__ bf16x8 frag(const char* img, int rs, int row, int col_elem) {
-  return *reinterpret_cast<const bf16x8*>(img + row * rs + col_elem * 2);
-}
-
-// rows [first, first + n) of one head's slice into a row-major image (zero at or past `limit`); optionally also its transpose
-// timg[d][r] (row stride TRS)
-__device__ __forceinline__ void mstage(char* img, int rs, char* timg, const bf16_t* __restrict__ base, int ld, int first, int n, int limit,
-                                       int hd) {
-  const int cpr = hd / 8;
-  for (int idx = threadIdx.x; idx < n * cpr; idx += 256) {
-    const int r = idx / cpr, ch = idx % cpr;
-    const int j = first + r;
-    uint4 v = make_uint4(0, 0, 0, 0);
-    if (j < limit) v = *reinterpret_cast<const uint4*>(base + (size_t)j * ld + ch * 8);
-    *reinterpret_cast<uint4*>(img + r * rs + ch * 16) = v;
-    if (timg) {
-      const bf16_t* e = reinterpret_cast<const bf16_t*>(&v);
-#pragma unroll
-      for (int t = 0; t < 8; ++t) *reinterpret_cast<bf16_t*>(timg + (ch * 8 + t) * TRS + r * 2) = e[t];
-    }
-  }
-}
-
-// acc[ct] (+)= X[x0 + 0..15] . Y[16 ct + 0..15]^T over kk k-steps of 32
-template <int NCT>
-__device__ __forceinline__ void mm_xyt(const char* X, int xrs, int x0, const char* Y, int yrs, int kk, int lane, f32x4 (&acc)[NCT]) {
-  const int l15 = lane & 15, g = lane >> 4;
-  for (int k = 0; k < kk; ++k) {
-    const bf16x8 a = frag(X, xrs, x0 + l15, 32 * k + 8 * g);
-#pragma unroll
-    for (int ct = 0; ct < NCT; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, frag(Y, yrs, 16 * ct + l15, 32 * k + 8 * g), acc[ct], 0, 0, 0);
-  }
-}
-
-// 16 x 32 coefficient tile (C layout, two 16-column halves) -> bf16 image W[16][32] of this wave (row stride TRS)
-__device__ __forceinline__ void put_coef(char* W, int lane, const float (&c)[2][4]) {
-  const int l15 = lane & 15, g = lane >> 4;
-#pragma unroll
-  for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) *reinterpret_cast<bf16_t*>(W + (4 * g + r) * TRS + (16 * ct + l15) * 2) = (bf16_t)c[ct][r];
-}
-
-__device__ __forceinline__ float g16_max(float v) {
-  v = fmaxf(v, __shfl_xor(v, 1, 64)); v = fmaxf(v, __shfl_xor(v, 2, 64)); v = fmaxf(v, __shfl_xor(v, 4, 64)); v = fmaxf(v, __shfl_xor(v, 8, 64));
-  return v;
-}
-__device__ __forceinline__ float g16_sum(float v) {
-  v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64); v += __shfl_xor(v, 8, 64);
-  return v;
-}
-
 template <int KK>
 __global__ __launch_bounds__(256) void full_mfma_fwd_kernel(const FullArgs a) {
   constexpr int NT = 2 * KK;          // 16-wide dim tiles of the head dim
@@ -449,7 +310,7 @@ __global__ __launch_bounds__(256) void full_mfma_fwd_kernel(const FullArgs a) {
   const int hd = a.hd, ld = 3 * a.D;
   const bf16_t* qbase = reinterpret_cast<const bf16_t*>(a.qkv) + (size_t)doc.base * ld + h * hd;
   char* W = Pw + w * 16 * TRS;
-  mstage(Qs, a.rs, nullptr, qbase, ld, q0, MQ, doc.nrows, hd);
+  attn_mstage(Qs, a.rs, nullptr, qbase, ld, q0, MQ, doc.nrows, hd);
   float m[4], l[4];
   f32x4 acc[NT];
 #pragma unroll
@@ -460,22 +321,11 @@ __global__ __launch_bounds__(256) void full_mfma_fwd_kernel(const FullArgs a) {
   for (int kt = 0; kt < nkt; ++kt) {
     const int j0 = kt * MK;
     __syncthreads();
-    mstage(Ks, a.rs, nullptr, qbase + a.D, ld, j0, MK, doc.len, hd);
-    {                                                  // V only as its transpose [dim][key]
-      const int cpr = hd / 8;
-      const bf16_t* vb = qbase + 2 * a.D;
-      for (int idx = threadIdx.x; idx < MK * cpr; idx += 256) {
-        const int r = idx / cpr, ch = idx % cpr, j = j0 + r;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (j < doc.len) v = *reinterpret_cast<const uint4*>(vb + (size_t)j * ld + ch * 8);
-        const bf16_t* e = reinterpret_cast<const bf16_t*>(&v);
-#pragma unroll
-        for (int t = 0; t < 8; ++t) *reinterpret_cast<bf16_t*>(Vt + (ch * 8 + t) * TRS + r * 2) = e[t];
-      }
-    }
+    attn_mstage(Ks, a.rs, nullptr, qbase + a.D, ld, j0, MK, doc.len, hd);
+    attn_mstage(nullptr, 0, Vt, qbase + 2 * a.D, ld, j0, MK, doc.len, hd);   // V only as its transpose [dim][key]
     __syncthreads();
     f32x4 s[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-    mm_xyt<2>(Qs, a.rs, 16 * w, Ks, a.rs, KK, lane, s);
+    attn_mm_xyt<2>(Qs, a.rs, 16 * w, Ks, a.rs, KK, lane, s);
     float p[2][4], alpha[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -485,7 +335,7 @@ __global__ __launch_bounds__(256) void full_mfma_fwd_kernel(const FullArgs a) {
         if (j0 + 16 * ct + l15 >= doc.len) s[ct][r] = -INFINITY;
         mt = fmaxf(mt, s[ct][r]);
       }
-      const float mn = fmaxf(m[r], g16_max(mt));       // finite: key j0 < len is in every visited tile
+      const float mn = fmaxf(m[r], lanes16_max(mt));       // finite: key j0 < len is in every visited tile
       alpha[r] = __expf(m[r] - mn);
       float ps = 0.f;
 #pragma unroll
@@ -495,16 +345,16 @@ __global__ __launch_bounds__(256) void full_mfma_fwd_kernel(const FullArgs a) {
         const int i = q0 + 16 * w + 4 * g + r, j = j0 + 16 * ct + l15;
         p[ct][r] = a.drop_thr ? (full_keep(a, doc.base + i, h, j) ? e * a.drop_scale : 0.f) : e;
       }
-      l[r] = l[r] * alpha[r] + g16_sum(ps);
+      l[r] = l[r] * alpha[r] + lanes16_sum(ps);
       m[r] = mn;
     }
 #pragma unroll
     for (int n = 0; n < NT; ++n)
 #pragma unroll
       for (int r = 0; r < 4; ++r) acc[n][r] *= alpha[r];
-    put_coef(W, lane, p);
+    attn_put_coef(W, lane, p);
     __syncthreads();
-    mm_xyt<NT>(W, TRS, 0, Vt, TRS, 1, lane, acc);
+    attn_mm_xyt<NT>(W, TRS, 0, Vt, TRS, 1, lane, acc);
   }
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
@@ -542,8 +392,8 @@ __global__ __launch_bounds__(256) void full_mfma_bwd_q_kernel(const FullArgs a) 
   const bf16_t* dobase = reinterpret_cast<const bf16_t*>(a.dctx) + (size_t)doc.base * a.D + h * hd;
   const bf16_t* obase = reinterpret_cast<const bf16_t*>(a.ctx) + (size_t)doc.base * a.D + h * hd;
   char* W = Pw + w * 16 * TRS;
-  mstage(Qs, a.rs, nullptr, qbase, ld, q0, MQ, doc.nrows, hd);
-  mstage(dOs, a.rs, nullptr, dobase, a.D, q0, MQ, doc.nrows, hd);
+  attn_mstage(Qs, a.rs, nullptr, qbase, ld, q0, MQ, doc.nrows, hd);
+  attn_mstage(dOs, a.rs, nullptr, dobase, a.D, q0, MQ, doc.nrows, hd);
   if (threadIdx.x < MQ) {                               // delta = dCtx . ctx (fixed order), lse; rows past the document: P = 0
     const int i = q0 + threadIdx.x;
     float d = 0.f, lv = INFINITY;
@@ -568,13 +418,13 @@ __global__ __launch_bounds__(256) void full_mfma_bwd_q_kernel(const FullArgs a) 
   for (int kt = 0; kt < nkt; ++kt) {
     const int j0 = kt * MK;
     __syncthreads();
-    mstage(Ks, a.rs, Kt, qbase + a.D, ld, j0, MK, doc.len, hd);
-    mstage(Vs, a.rs, nullptr, qbase + 2 * a.D, ld, j0, MK, doc.len, hd);
+    attn_mstage(Ks, a.rs, Kt, qbase + a.D, ld, j0, MK, doc.len, hd);
+    attn_mstage(Vs, a.rs, nullptr, qbase + 2 * a.D, ld, j0, MK, doc.len, hd);
     __syncthreads();
     f32x4 s[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
     f32x4 dp[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-    mm_xyt<2>(Qs, a.rs, 16 * w, Ks, a.rs, KK, lane, s);
-    mm_xyt<2>(dOs, a.rs, 16 * w, Vs, a.rs, KK, lane, dp);
+    attn_mm_xyt<2>(Qs, a.rs, 16 * w, Ks, a.rs, KK, lane, s);
+    attn_mm_xyt<2>(dOs, a.rs, 16 * w, Vs, a.rs, KK, lane, dp);
     float ds[2][4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -588,9 +438,9 @@ __global__ __launch_bounds__(256) void full_mfma_bwd_q_kernel(const FullArgs a) 
         ds[ct][r] = p * (d - row_s[MQ + ri]);
       }
     }
-    put_coef(W, lane, ds);
+    attn_put_coef(W, lane, ds);
     __syncthreads();
-    mm_xyt<NT>(W, TRS, 0, Kt, TRS, 1, lane, acc);
+    attn_mm_xyt<NT>(W, TRS, 0, Kt, TRS, 1, lane, acc);
   }
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
@@ -631,16 +481,16 @@ __global__ __launch_bounds__(256) void full_mfma_bwd_kv_kernel(const FullArgs a)
 #pragma unroll
   for (int n = 0; n < NT; ++n) dk[n] = dv[n] = f32x4{0.f, 0.f, 0.f, 0.f};
   if (k0 < doc.len) {                           // padded keys (padded layout only): gradient 0
-    mstage(Ks, a.rs, nullptr, qbase + a.D, ld, k0, MQ, doc.len, hd);
-    mstage(Vs, a.rs, nullptr, qbase + 2 * a.D, ld, k0, MQ, doc.len, hd);
+    attn_mstage(Ks, a.rs, nullptr, qbase + a.D, ld, k0, MQ, doc.len, hd);
+    attn_mstage(Vs, a.rs, nullptr, qbase + 2 * a.D, ld, k0, MQ, doc.len, hd);
     char* PW = Pw + w * 16 * TRS;
     char* SW = Sw + w * 16 * TRS;
     const int nqt = (doc.nrows + MK - 1) / MK;
     for (int qt = 0; qt < nqt; ++qt) {
       const int i0 = qt * MK;
       __syncthreads();
-      mstage(Qs, a.rs, Qt, qbase, ld, i0, MK, doc.nrows, hd);
-      mstage(dOs, a.rs, dOt, dobase, a.D, i0, MK, doc.nrows, hd);
+      attn_mstage(Qs, a.rs, Qt, qbase, ld, i0, MK, doc.nrows, hd);
+      attn_mstage(dOs, a.rs, dOt, dobase, a.D, i0, MK, doc.nrows, hd);
       if (threadIdx.x < MK) {
         const int i = i0 + threadIdx.x;
         const bool ok = i < doc.nrows;
@@ -650,8 +500,8 @@ __global__ __launch_bounds__(256) void full_mfma_bwd_kv_kernel(const FullArgs a)
       __syncthreads();
       f32x4 s[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
       f32x4 dp[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-      mm_xyt<2>(Ks, a.rs, 16 * w, Qs, a.rs, KK, lane, s);      // S^T: rows = keys, columns = queries
-      mm_xyt<2>(Vs, a.rs, 16 * w, dOs, a.rs, KK, lane, dp);    // dP^T
+      attn_mm_xyt<2>(Ks, a.rs, 16 * w, Qs, a.rs, KK, lane, s);      // S^T: rows = keys, columns = queries
+      attn_mm_xyt<2>(Vs, a.rs, 16 * w, dOs, a.rs, KK, lane, dp);    // dP^T
       float pt[2][4], st[2][4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -666,11 +516,11 @@ __global__ __launch_bounds__(256) void full_mfma_bwd_kv_kernel(const FullArgs a)
           st[ct][r] = p * (dp[ct][r] * keep - del_s[ci]);
         }
       }
-      put_coef(PW, lane, pt);
-      put_coef(SW, lane, st);
+      attn_put_coef(PW, lane, pt);
+      attn_put_coef(SW, lane, st);
       __syncthreads();
-      mm_xyt<NT>(PW, TRS, 0, dOt, TRS, 1, lane, dv);
-      mm_xyt<NT>(SW, TRS, 0, Qt, TRS, 1, lane, dk);
+      attn_mm_xyt<NT>(PW, TRS, 0, dOt, TRS, 1, lane, dv);
+      attn_mm_xyt<NT>(SW, TRS, 0, Qt, TRS, 1, lane, dk);
     }
   }
 #pragma unroll
@@ -690,12 +540,6 @@ __global__ __launch_bounds__(256) void full_mfma_bwd_kv_kernel(const FullArgs a)
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-static int full_row_stride(int hd, int esize) {
-  int bytes = ((hd * esize + 15) / 16) * 16;
-  if (((bytes / 16) & 1) == 0) bytes += 16;   // 16 B x odd: the rows of one column hit distinct 16-byte bank slots
-  return bytes;
-}
-
 static size_t full_generic_lds(int rs);
 
 static int full_fill(FullArgs& a, int dtype, int B, int L, int D, int heads, const char* who) {
@@ -708,45 +552,11 @@ static int full_fill(FullArgs& a, int dtype, int B, int L, int D, int heads, con
   MTS_UNSUPPORTED((long)B * L * heads < (1L << 31) && (long)B * L * 3 * D < (1L << 31), "%s: problem too large for 32-bit row indexing", who);
   memset(&a, 0, sizeof(a));
   a.B = B; a.L = L; a.D = D; a.heads = heads; a.hd = hd;
-  a.rs = full_row_stride(hd, dtype == MTS_F32 ? 4 : 2);
+  a.rs = attn_row_stride(hd, dtype == MTS_F32 ? 4 : 2);
   MTS_UNSUPPORTED(full_generic_lds(a.rs) <= 160 * 1024, "%s: head dim %d in %s needs %zu bytes of LDS (> 160 KiB)", who, hd,
                   dtype == MTS_F32 ? "fp32" : "bf16", full_generic_lds(a.rs));
   a.q_scale = 1.f;
   a.drop_scale = 1.f;
-  return MTS_OK;
-}
-
-static int full_set_dropout(FullArgs& a, float p, uint64_t seed, const char* who) {
-  MTS_CHECK_ARG(p >= 0.f && p < 1.f, "%s: dropout probability has to be between 0 and 1, but got %f", who, (double)p);
-  if (p > 0.f) {
-    a.drop_thr = (uint32_t)std::max<double>(1.0, std::min<double>(4294967295.0, (double)p * 4294967296.0));
-    a.drop_scale = 1.0f / (1.0f - p);
-    a.drop_seed = seed;
-  }
-  return MTS_OK;
-}
-
-// The dynamic-LDS limit is a property of (kernel, device).  It is set on the calling thread's current device the first time a
-// launch there needs more than it holds; the (kernel, device, bytes) triples already set are remembered, so a steady-state step
-// makes no attribute call.
-static std::mutex g_lds_mu;
-struct LdsSet { const void* fn; int dev; size_t bytes; };
-static std::vector<LdsSet> g_lds_set;
-
-template <typename K> static int full_lds(K kernel, size_t bytes, const char* who) {
-  MTS_UNSUPPORTED(bytes <= 160 * 1024, "%s: needs %zu bytes of LDS (> 160 KiB): head dim too large for this dtype", who, bytes);
-  if (bytes <= 64 * 1024) return MTS_OK;
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) { mts_set_error("%s: hipGetDevice: %s", who, hipGetErrorString(e)); return MTS_ERR_LAUNCH; }
-  std::lock_guard<std::mutex> lk(g_lds_mu);
-  for (const LdsSet& x : g_lds_set)
-    if (x.fn == (const void*)kernel && x.dev == dev && x.bytes >= bytes) return MTS_OK;
-  e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e != hipSuccess) { mts_set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e)); return MTS_ERR_LAUNCH; }
-  for (LdsSet& x : g_lds_set)
-    if (x.fn == (const void*)kernel && x.dev == dev) { x.bytes = bytes; return MTS_OK; }
-  g_lds_set.push_back(LdsSet{(const void*)kernel, dev, bytes});
   return MTS_OK;
 }
 
@@ -775,7 +585,7 @@ static int full_mfma_fwd_launch(const FullArgs& a, hipStream_t st) {
   const int nblocks = ceil_div(a.L, MQ) * a.heads * a.B;
   int rc = MTS_OK;
 #define FWD_CALL(K)                                                                                   \
-  rc = full_lds(full_mfma_fwd_kernel<K>, lds, "mts_full_attn_fwd");                                  \
+  rc = mts_dyn_lds(full_mfma_fwd_kernel<K>, lds, "mts_full_attn_fwd");                                  \
   if (!rc) hipLaunchKernelGGL(full_mfma_fwd_kernel<K>, dim3(nblocks), dim3(256), lds, st, a);
   FULL_KK_SWITCH(a.hd / 32, FWD_CALL)
 #undef FWD_CALL
@@ -789,8 +599,8 @@ static int full_mfma_bwd_launch(const FullArgs& a, hipStream_t st) {
   const int nblocks = ceil_div(a.L, MQ) * a.heads * a.B;
   int rc = MTS_OK;
 #define BWD_CALL(K)                                                                                   \
-  rc = full_lds(full_mfma_bwd_q_kernel<K>, lq, "mts_full_attn_bwd(q)");                              \
-  if (!rc) rc = full_lds(full_mfma_bwd_kv_kernel<K>, lkv, "mts_full_attn_bwd(kv)");                  \
+  rc = mts_dyn_lds(full_mfma_bwd_q_kernel<K>, lq, "mts_full_attn_bwd(q)");                              \
+  if (!rc) rc = mts_dyn_lds(full_mfma_bwd_kv_kernel<K>, lkv, "mts_full_attn_bwd(kv)");                  \
   if (!rc) {                                                                                          \
     hipLaunchKernelGGL(full_mfma_bwd_q_kernel<K>, dim3(nblocks), dim3(256), lq, st, a);              \
     hipLaunchKernelGGL(full_mfma_bwd_kv_kernel<K>, dim3(nblocks), dim3(256), lkv, st, a);            \
@@ -807,7 +617,7 @@ static int full_fwd_launch(const FullArgs& a, hipStream_t st) {
   const size_t lds = (size_t)2 * FT * a.rs + (size_t)FT * PS * sizeof(float);
   const int nblocks = ceil_div(a.L, FT) * a.heads * a.B;
   auto k = a.hd > 256 ? full_fwd_kernel<T, 16> : full_fwd_kernel<T, 8>;     // 8 lanes x MAXU chunks of 4 cover the head dim
-  int rc = full_lds(k, lds, "mts_full_attn_fwd");
+  int rc = mts_dyn_lds(k, lds, "mts_full_attn_fwd");
   if (rc) return rc;
   hipLaunchKernelGGL(k, dim3(nblocks), dim3(256), lds, st, a);
   MTS_LAUNCH_CHECK("mts_full_attn_fwd");
@@ -821,8 +631,8 @@ static int full_bwd_launch(const FullArgs& a, hipStream_t st) {
   const size_t lds_kv = (size_t)4 * FT * a.rs + (size_t)(2 * FT * PS + 2 * FT) * sizeof(float);
   auto kq = a.hd > 256 ? full_bwd_q_kernel<T, 16> : full_bwd_q_kernel<T, 8>;
   auto kkv = a.hd > 256 ? full_bwd_kv_kernel<T, 16> : full_bwd_kv_kernel<T, 8>;
-  int rc = full_lds(kq, lds_q, "mts_full_attn_bwd(q)");
-  if (!rc) rc = full_lds(kkv, lds_kv, "mts_full_attn_bwd(kv)");
+  int rc = mts_dyn_lds(kq, lds_q, "mts_full_attn_bwd(q)");
+  if (!rc) rc = mts_dyn_lds(kkv, lds_kv, "mts_full_attn_bwd(kv)");
   if (rc) return rc;
   hipLaunchKernelGGL(kq, dim3(nblocks), dim3(256), lds_q, st, a);
   hipLaunchKernelGGL(kkv, dim3(nblocks), dim3(256), lds_kv, st, a);
@@ -837,7 +647,7 @@ extern "C" int mts_full_attn_fwd(void* stream, int dtype, int B, int L, int D, i
   if (rc) return rc;
   MTS_CHECK_ARG(qkv && ctx && lse, "mts_full_attn_fwd: null pointer");
   MTS_CHECK_ARG(!row0 || lengths, "mts_full_attn_fwd: packed rows (row0) need lengths");
-  rc = full_set_dropout(a, drop_p, drop_seed, "mts_full_attn_fwd");
+  rc = attn_set_dropout(a, drop_p, drop_seed, "mts_full_attn_fwd");
   if (rc) return rc;
   a.qkv = qkv; a.lengths = lengths; a.ctx = ctx; a.lse = lse; a.row0 = row0;
   if (full_use_mfma(a, dtype)) return full_mfma_fwd_launch(a, (hipStream_t)stream);
@@ -857,7 +667,7 @@ extern "C" int mts_full_attn_bwd(void* stream, int dtype, int B, int L, int D, i
   if (rc) return rc;
   MTS_CHECK_ARG(qkv && lse && ctx && dctx && dqkv && workspace, "mts_full_attn_bwd: null pointer (workspace is required)");
   MTS_CHECK_ARG(!row0 || (lengths && n_rows > 0 && n_rows <= B * L), "mts_full_attn_bwd: packed rows (row0) need lengths and 0 < n_rows <= B*L");
-  rc = full_set_dropout(a, drop_p, drop_seed, "mts_full_attn_bwd");
+  rc = attn_set_dropout(a, drop_p, drop_seed, "mts_full_attn_bwd");
   if (rc) return rc;
   a.qkv = qkv; a.lengths = lengths; a.lse = const_cast<float*>(lse); a.ctx = const_cast<void*>(ctx); a.dctx = dctx; a.dqkv = dqkv;
   a.delta = (float*)workspace; a.row0 = row0; a.q_scale = q_scale;

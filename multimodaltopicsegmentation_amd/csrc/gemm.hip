@@ -14,7 +14,6 @@
 // The accumulator tile is computed TRANSPOSED (the W fragment is the MFMA A operand) so that each lane
 // ends up with 4 consecutive output columns of one row: bias/residual/aux/C are accessed as 8/16-byte
 // vectors in the epilogue.
-#include <atomic>
 #include <algorithm>
 #include <math.h>
 #include <stdlib.h>
@@ -45,11 +44,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(const GemmArgs a) {
   const int ntn = (a.N + BN - 1) / BN;
   const int ntm = (a.M + BM - 1) / BM;
   const int nt = ntn * ntm;
-  int bid = blockIdx.x;
-  {
-    const int q = nt >> 3, rr = nt & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + idx;
-  }
+  int bid = xcd_remap(blockIdx.x, nt);
   // ... walking the SHORTER side of the tile grid first: with 2 x 14 tiles (feed-forward weight gradient, M = 256) the two tiles of a column
   // run side by side on one XCD and the wide operand's panel is fetched once, not once per tile row
   const int bm0 = (ntm < ntn ? bid % ntm : bid / ntn) * BM;
@@ -791,11 +786,7 @@ static void launch_bf16(const GemmArgs& a, int splits, hipStream_t st) {
     const bool deep = g_gemm_deep && (size_t)nt * splits <= 256 && a.ksplit >= 4 * BK;
     b.nbuf = deep ? 4 : 2;
     auto k = gemm_bf16_kernel<LAYOUT, TC, true>;
-    static std::atomic<bool> attr_set{false};      // idempotent, process-wide: two threads racing here set the same attribute twice
-    if (deep && !attr_set.load(std::memory_order_acquire)) {
-      if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * TILE_BYTES) != hipSuccess) b.nbuf = 2;
-      else attr_set.store(true, std::memory_order_release);
-    }
+    if (deep && mts_dyn_lds(k, 8 * TILE_BYTES, "gemm") != MTS_OK) b.nbuf = 2;     // no opt-in: the two-buffer form fits the default
     hipLaunchKernelGGL(k, dim3(nt, 1, splits), dim3(256), (b.nbuf == 4 ? 8 : 4) * TILE_BYTES, st, b);
   } else {
     hipLaunchKernelGGL((gemm_bf16_kernel<LAYOUT, TC, false>), dim3(nt, 1, splits), dim3(256), 4 * TILE_BYTES, st, a);

@@ -270,8 +270,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_224_kernel(const GemmArgs a)
   // the 32 tiles an XCD works on at a time form a 4 x 8 block (4 A panels + 8 B panels per K-step) instead of a
   // 1.3 x 24 strip that streams ALL of the weight matrix through every L2 in every round.
   auto tile_origin = [&](int t, int& bm0, int& bn0) {
-    const int q = nt >> 3, rr = nt & 7, xcd = t & 7, idx = t >> 3;
-    const int id = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + idx;
+    const int id = xcd_remap(t, nt);
     if (a.order == 0) { bm0 = (id / ntn) * 256; bn0 = (id % ntn) * BN224; return; }
     const int band = id / (4 * ntn), within = id - band * 4 * ntn;
     const int rows = min(4, ntm - band * 4);
@@ -667,12 +666,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_224_kernel(const GemmArgs a)
 template <int LAYOUT, typename TC, bool PERSIST, bool MIDBAR>
 static int launch_one_p(const GemmArgs& a, int splits, hipStream_t st) {
   auto k = gemm_bf16_224_kernel<LAYOUT, TC, PERSIST, MIDBAR>;
-  static std::atomic<bool> attr_set{false};   // idempotent process-wide attribute: a race sets it twice
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);
-    if (e != hipSuccess) { mts_set_error("gemm224: hipFuncSetAttribute: %s", hipGetErrorString(e)); return MTS_ERR_LAUNCH; }
-    attr_set = true;
-  }
+  if (int rc = mts_dyn_lds(k, LDS_TOTAL, "gemm224")) return rc;
   const int nt = ceil_div(a.M, 256) * (a.N / BN224);
   const int gx = (PERSIST && splits == 1) ? std::min(nt, 256) : nt;
 #ifdef MTS_GEMM_STAMPS

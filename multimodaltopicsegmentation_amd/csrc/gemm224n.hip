@@ -74,9 +74,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_224n_kernel(const GemmArgs a
   const bf16_t* __restrict__ B = reinterpret_cast<const bf16_t*>(a.B);
   int bm0, bn0;
   {
-    const int t = blockIdx.x;
-    const int qq = nt >> 3, rr = nt & 7, xcd = t & 7, idx = t >> 3;
-    const int id = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + idx;
+    const int id = xcd_remap(blockIdx.x, nt);
     if (a.order == 0) { bm0 = (id / ntn) * 256; bn0 = (id % ntn) * N_BN; }
     else {
       const int band = id / (4 * ntn), within = id - band * 4 * ntn;
@@ -309,12 +307,7 @@ bool mts_gemm224n_applies(const GemmArgs& a, int layout, bool c_is_f32, int spli
 int mts_launch_gemm224n(const GemmArgs& a, int layout, bool c_is_f32, int splits, hipStream_t st) {
   if (!mts_gemm224n_applies(a, layout, c_is_f32, splits)) return -1;
   auto k = gemm_bf16_224n_kernel;
-  static std::atomic<bool> attr_set{false};
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, N_LDS);
-    if (e != hipSuccess) { mts_set_error("gemm224n: hipFuncSetAttribute: %s", hipGetErrorString(e)); return MTS_ERR_LAUNCH; }
-    attr_set = true;
-  }
+  if (int rc = mts_dyn_lds(k, N_LDS, "gemm224n")) return rc;
   const int nt = (a.M / 256) * (a.N / N_BN);
   hipLaunchKernelGGL(k, dim3(nt), dim3(256), N_LDS, st, a);
   return MTS_OK;

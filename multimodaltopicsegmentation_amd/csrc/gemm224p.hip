@@ -70,8 +70,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_224p_kernel(const GemmArgs a
   // take ids first + idx, first + idx + wx, ..: at any time the XCD works on wx consecutive ids = (with the band order) a 4 x 8 block of tiles
   const int G = gridDim.x, xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
   const int wx = (G - xcd + 7) >> 3;                          // workgroups of this launch on my XCD
-  const int q = nt >> 3, rr = nt & 7;
-  const int first = xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q, cnt = xcd < rr ? q + 1 : q;
+  const int first = xcd_remap(xcd, nt), cnt = (nt >> 3) + (xcd < (nt & 7) ? 1 : 0);   // block id xcd heads the XCD's run
   auto origin = [&](int j, int& bm0, int& bn0) {              // j: index inside my XCD's run
     const int id = first + j;
     if (a.order == 0) { bm0 = (id / ntn) * 256; bn0 = (id % ntn) * P_BN; return; }
@@ -286,12 +285,7 @@ int mts_launch_gemm224p(const GemmArgs& a, int layout, bool c_is_f32, int splits
                   (!(a.epi & MTS_EPI_BIAS) || ((uintptr_t)a.bias & 15) == 0);
   if (!ok) return -1;
   auto k = gemm_bf16_224p_kernel;
-  static std::atomic<bool> attr_set{false};
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, P_LDS);
-    if (e != hipSuccess) { mts_set_error("gemm224p: hipFuncSetAttribute: %s", hipGetErrorString(e)); return MTS_ERR_LAUNCH; }
-    attr_set = true;
-  }
+  if (int rc = mts_dyn_lds(k, P_LDS, "gemm224p")) return rc;
   const int nt = (a.M / 256) * (a.N / P_BN);
   static std::atomic<int> ncu{0};
   if (!ncu) {

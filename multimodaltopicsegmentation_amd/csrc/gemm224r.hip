@@ -62,9 +62,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_224d_kernel(const GemmArgs a
   const bf16_t* __restrict__ B = reinterpret_cast<const bf16_t*>(a.B);
   int bm0, bn0;
   {
-    const int t = blockIdx.x;
-    const int q = nt >> 3, rr = nt & 7, xcd = t & 7, idx = t >> 3;
-    const int id = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + idx;
+    const int id = xcd_remap(blockIdx.x, nt);
     if (a.order == 0) { bm0 = (id / ntn) * 256; bn0 = (id % ntn) * R_BN; }
     else {
       const int band = id / (4 * ntn), within = id - band * 4 * ntn;
@@ -245,12 +243,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_224d_kernel(const GemmArgs a
 
 static int d_launch(const GemmArgs& a, hipStream_t st) {
   auto k = gemm_bf16_224d_kernel;
-  static std::atomic<bool> attr_set{false};
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, R_LDS);
-    if (e != hipSuccess) { mts_set_error("gemm224d: hipFuncSetAttribute: %s", hipGetErrorString(e)); return MTS_ERR_LAUNCH; }
-    attr_set = true;
-  }
+  if (int rc = mts_dyn_lds(k, R_LDS, "gemm224d")) return rc;
   const int nt = (a.M / 256) * (a.N / R_BN);
   hipLaunchKernelGGL(k, dim3(nt), dim3(256), R_LDS, st, a);
   return MTS_OK;

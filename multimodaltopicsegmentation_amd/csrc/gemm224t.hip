@@ -100,9 +100,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_224t_kernel(const GemmArgs a
   int bm0, bn0, z;
   bool second;
   {
-    const int t = blockIdx.x, ngrid = gridDim.x;
-    const int qq = ngrid >> 3, rr = ngrid & 7, xcd = t & 7, idx = t >> 3;
-    int id = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + idx;
+    int id = xcd_remap(blockIdx.x, gridDim.x);
     second = PAIR && id >= ntot;                        // (pair launch: gridDim.x = 2 ntot)
     if (second) id -= ntot;
     z = id / nt;
@@ -284,12 +282,7 @@ bool mts_gemm224t_applies(const GemmArgs& a, int layout, bool c_is_f32, int spli
 int mts_launch_gemm224t(const GemmArgs& a, int layout, bool c_is_f32, int splits, hipStream_t st) {
   if (!mts_gemm224t_applies(a, layout, c_is_f32, splits)) return -1;
   auto k = gemm_bf16_224t_kernel<false>;
-  static std::atomic<bool> attr_set{false};
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS);
-    if (e != hipSuccess) { mts_set_error("gemm224t: hipFuncSetAttribute: %s", hipGetErrorString(e)); return MTS_ERR_LAUNCH; }
-    attr_set = true;
-  }
+  if (int rc = mts_dyn_lds(k, T_LDS, "gemm224t")) return rc;
   const int nt = (a.M / 256) * (a.N / T_BN);
   if (a.chain) {                                       // the arrival tickets of the in-launch combine: zeroed on the stream, every call
     hipError_t e = hipMemsetAsync(a.chain, 0, ((size_t)nt * sizeof(unsigned) + 15) & ~(size_t)15, st);
@@ -303,12 +296,7 @@ int mts_launch_gemm224t(const GemmArgs& a, int layout, bool c_is_f32, int splits
 int mts_launch_gemm224t_pair(const GemmArgs& a, int splits, const void* A2, const void* B2, float* slab2, hipStream_t st) {
   if (!mts_gemm224t_applies(a, MTS_TN, true, splits) || !a.slab || a.chain || !A2 || !B2 || !slab2 || (((uintptr_t)A2 | (uintptr_t)B2) & 15)) return -1;
   auto k = gemm_bf16_224t_kernel<true>;
-  static std::atomic<bool> attr_set{false};
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS);
-    if (e != hipSuccess) { mts_set_error("gemm224t: hipFuncSetAttribute: %s", hipGetErrorString(e)); return MTS_ERR_LAUNCH; }
-    attr_set = true;
-  }
+  if (int rc = mts_dyn_lds(k, T_LDS, "gemm224t")) return rc;
   const int nt = (a.M / 256) * (a.N / T_BN);
   hipLaunchKernelGGL(k, dim3(2 * nt * splits), dim3(256), T_LDS, st, a, splits, A2, B2, slab2);
   return MTS_OK;

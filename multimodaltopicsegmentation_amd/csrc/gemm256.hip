@@ -137,8 +137,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_256_kernel(const GemmArgs a)
   // persistent over output tiles: workgroup w takes tiles w, w + gridDim.x, ...; the XCD remap keeps the tiles
   // that run at the same time on one XCD adjacent in N (they share the A panel in that XCD's L2)
   auto tile_origin = [&](int t, int& bm0, int& bn0) {
-    const int q = nt >> 3, rr = nt & 7, xcd = t & 7, idx = t >> 3;
-    const int id = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + idx;
+    const int id = xcd_remap(t, nt);
     bm0 = (id / ntn) * 256;
     bn0 = (id % ntn) * 256;
   };
@@ -302,12 +301,7 @@ template <int LAYOUT, typename TC>
 static int launch_one(const GemmArgs& a, int splits, hipStream_t st) {
   constexpr bool PERSIST = sizeof(TC) != 2;
   auto k = gemm_bf16_256_kernel<LAYOUT, TC, PERSIST>;
-  static std::atomic<bool> attr_set{false};   // idempotent process-wide attribute: a race sets it twice
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);
-    if (e != hipSuccess) { mts_set_error("gemm256: hipFuncSetAttribute: %s", hipGetErrorString(e)); return MTS_ERR_LAUNCH; }
-    attr_set = true;
-  }
+  if (int rc = mts_dyn_lds(k, LDS_TOTAL, "gemm256")) return rc;
   const int nt = ceil_div(a.M, 256) * ceil_div(a.N, 256);
   const int gx = (PERSIST && splits == 1) ? std::min(nt, 256) : nt;      // fp32 C: persistent over tiles when K is not split
   hipLaunchKernelGGL(k, dim3(gx, 1, splits), dim3(512), LDS_TOTAL, st, a);

@@ -1,4 +1,4 @@
-// Pieces shared by the two bf16 MFMA GEMM kernels (gemm.hip: 128x128 tile; gemm256.hip: 256x256 tile).
+// Pieces shared by the bf16 MFMA GEMM translation units (every gemm*.hip and ffn_fused.hip).
 #pragma once
 #include "common.h"
 

@@ -342,12 +342,12 @@ static int lstm_bwd_impl(int part, void* stream, int dtype, int B, int L, int H,
       dim3 grid(ceil_div(B, LSTM_DG), ndir), block(lstm_threads(H));
       if (dtype == MTS_F32) {
         auto k = lstm_bwd_kernel<float>;
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (int rc = mts_dyn_lds(k, lds, who)) return rc;
         hipLaunchKernelGGL(k, grid, block, lds, st, B, L, H, ndir, w_hh, lengths, (const float*)out, (const float*)gates, cells, (const float*)dout,
                            (float*)dxproj, (float*)hprev);
       } else {
         auto k = lstm_bwd_kernel<bf16_t>;
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (int rc = mts_dyn_lds(k, lds, who)) return rc;
         hipLaunchKernelGGL(k, grid, block, lds, st, B, L, H, ndir, w_hh, lengths, (const bf16_t*)out, (const bf16_t*)gates, cells, (const bf16_t*)dout,
                            (bf16_t*)dxproj, (bf16_t*)hprev);
       }

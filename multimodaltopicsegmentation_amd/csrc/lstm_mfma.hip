@@ -454,14 +454,7 @@ int mts_lstm_mfma_fwd(hipStream_t st, int B, int L, int H, int ndir, const void*
   constexpr int KS = 8;
   const size_t lds = 2 * LM_DOCS * (H + 8) * 2 + (size_t)KS * LM_FWD_LT * KS * 1024 + (size_t)4 * H * sizeof(float);
   auto k = lstm_fwd_mfma_kernel<KS, LM_FWD_RT, LM_FWD_LT>;
-  static std::atomic<bool> attr{false};
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-      mts_set_error("lstm_mfma_fwd: cannot reserve %zu bytes of LDS", lds);
-      return MTS_ERR_LAUNCH;
-    }
-    attr = true;
-  }
+  if (int rc = mts_dyn_lds(k, lds, "lstm_mfma_fwd")) return rc;
   static int xflags = -1;
   if (xflags < 0) { const char* e = getenv("MTS_LSTM_EXP"); xflags = e ? atoi(e) : 0; }
   hipLaunchKernelGGL(k, dim3(ceil_div(B, LM_DOCS), ndir), dim3(KS * 64), lds, st, B, L, ndir, (const bf16_t*)xproj, (const bf16_t*)wb, b_hh, lengths,
@@ -478,14 +471,7 @@ int mts_lstm_mfma_bwd(hipStream_t st, int B, int L, int H, int ndir, const float
   constexpr int KS = 8;
   const size_t lds = 2 * LM_DOCS * (4 * H + 8) * 2 + (size_t)KS * LM_BWD_LT * KS * 1024;
   auto k = lstm_bwd_mfma_kernel<KS, LM_BWD_RT, LM_BWD_LT>;
-  static std::atomic<bool> attr{false};
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-      mts_set_error("lstm_mfma_bwd: cannot reserve %zu bytes of LDS", lds);
-      return MTS_ERR_LAUNCH;
-    }
-    attr = true;
-  }
+  if (int rc = mts_dyn_lds(k, lds, "lstm_mfma_bwd")) return rc;
   hipLaunchKernelGGL(k, dim3(ceil_div(B, LM_DOCS), ndir), dim3(KS * 64), lds, st, B, L, ndir, (const bf16_t*)wT, lengths, (const bf16_t*)out,
                      (const bf16_t*)gates, cells, (const bf16_t*)dout, (bf16_t*)dxproj, (bf16_t*)hprev);
   MTS_LAUNCH_CHECK("mts_lstm_bwd(mfma)");

@@ -388,14 +388,7 @@ int mts_lstm_pair_fwd(hipStream_t st, int B, int L, int H, int ndir, const void*
   if (hipMemsetAsync(xch, 0, pair_xbytes(B, ndir) + 256, st) != hipSuccess) { mts_set_error("lstm_pair: memset failed"); return MTS_ERR_LAUNCH; }
   const size_t lds = (size_t)LP_GROUPS * 2 * LP_DOCS * (H + 8) * 2 + (size_t)4 * (H / 2) * sizeof(float) + (size_t)KS * KS * 1024;
   auto k = lstm_fwd_pair_kernel<KS>;
-  static std::atomic<bool> attr{false};
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-      mts_set_error("lstm_pair_fwd: cannot reserve %zu bytes of LDS", lds);
-      return MTS_ERR_LAUNCH;
-    }
-    attr = true;
-  }
+  if (int rc = mts_dyn_lds(k, lds, "lstm_pair_fwd")) return rc;
   static int xflags = -1;
   if (xflags < 0) { const char* e = getenv("MTS_LSTM_EXP"); xflags = e ? atoi(e) : 0; }
   if (int rc = lp_ensure_sticky()) return rc;
@@ -1139,14 +1132,7 @@ int mts_lstm_pair_bwd(hipStream_t st, int B, int L, int H, int ndir, const float
   }
   const size_t lds = (size_t)2 * LP_DOCS * ((4 * HH + 8) * 2) + (size_t)KS * (KT / 2) * 1024;
   auto k = lstm_bwd_pair_kernel<KS>;
-  static std::atomic<bool> attr{false};
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-      mts_set_error("lstm_pair_bwd: cannot reserve %zu bytes of LDS", lds);
-      return MTS_ERR_LAUNCH;
-    }
-    attr = true;
-  }
+  if (int rc = mts_dyn_lds(k, lds, "lstm_pair_bwd")) return rc;
   if (int rc = lp_ensure_sticky()) return rc;
   const int docs_per_launch = std::max(1, g_max_pairs / ndir) * LP_DOCS * LP_GROUPS;
   for (int b0 = 0; b0 < B; b0 += docs_per_launch) {

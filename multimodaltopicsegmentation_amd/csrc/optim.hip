@@ -4,6 +4,7 @@
 #include <stdarg.h>
 #include <algorithm>
 #include <math.h>
+#include <mutex>
 #include "common.h"
 
 static thread_local char g_err[512] = "";
@@ -14,6 +15,47 @@ void mts_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 extern "C" const char* mts_last_error(void) { return g_err; }
+
+// The dynamic-LDS limit is a property of (kernel, device): g_lds remembers the bytes set per kernel and device.  Entries are
+// appended under the mutex and published through g_lds_n, so the steady-state path only reads atomics.  A kernel or device
+// the table has no room for is opted in on every launch.
+enum { LDS_KERNELS = 256, LDS_DEVICES = 16 };
+struct LdsEntry { const void* fn; std::atomic<uint32_t> bytes[LDS_DEVICES]; };
+static LdsEntry g_lds[LDS_KERNELS];
+static std::atomic<int> g_lds_n{0};
+static std::mutex g_lds_mu;
+
+static LdsEntry* lds_find(const void* kernel, int n) {
+  for (int i = 0; i < n; ++i)
+    if (g_lds[i].fn == kernel) return &g_lds[i];
+  return nullptr;
+}
+
+int mts_dyn_lds(const void* kernel, size_t bytes, const char* who) {
+  MTS_UNSUPPORTED(bytes <= 160 * 1024, "%s: needs %zu bytes of LDS (> 160 KiB)", who, bytes);
+  if (bytes <= 64 * 1024) return MTS_OK;
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) { mts_set_error("%s: hipGetDevice: %s", who, hipGetErrorString(e)); return MTS_ERR_LAUNCH; }
+  const bool tracked = dev >= 0 && dev < LDS_DEVICES;
+  LdsEntry* x = tracked ? lds_find(kernel, g_lds_n.load(std::memory_order_acquire)) : nullptr;
+  if (x && x->bytes[dev].load(std::memory_order_acquire) >= bytes) return MTS_OK;
+  std::lock_guard<std::mutex> lk(g_lds_mu);
+  if (tracked && !x) {
+    const int n = g_lds_n.load(std::memory_order_relaxed);
+    x = lds_find(kernel, n);
+    if (!x && n < LDS_KERNELS) {
+      x = &g_lds[n];
+      x->fn = kernel;
+      g_lds_n.store(n + 1, std::memory_order_release);
+    }
+  }
+  if (x && x->bytes[dev].load(std::memory_order_relaxed) >= bytes) return MTS_OK;    // another thread got here first
+  e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (e != hipSuccess) { mts_set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e)); return MTS_ERR_LAUNCH; }
+  if (x) x->bytes[dev].store((uint32_t)bytes, std::memory_order_release);
+  return MTS_OK;
+}
 extern "C" const char* mts_version(void) { return "mts-hip 1 gfx950"; }
 
 // Gradient clipping (Lightning's Trainer(gradient_clip_val, gradient_clip_algorithm) -> torch.nn.utils.clip_grad_norm_ / clip_grad_value_)

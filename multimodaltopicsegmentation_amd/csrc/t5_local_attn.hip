@@ -10,7 +10,7 @@
 // (padded v rows included).  Padded rows carry no gradient (they never reach a valid row or the loss), so the backward writes dq = 0
 // for them, dk = dv = 0 for padded keys, and never reads their dctx.
 //
-// Work decomposition as full_attn.hip's generic kernels: one 256-thread workgroup per (document, head, tile of 32 rows); lane = (row
+// Work decomposition on the helpers of attn_tile.h: one 256-thread workgroup per (document, head, tile of 32 rows); lane = (row
 // t = tid/8, group g = tid%8); score-type products are 16-byte LDS dot products (v_dot2_f32_bf16 on bf16 pairs), accumulations stream
 // 4-element chunks of the head dim.  The key (query) tiles a workgroup visits start at the first key (query) any of its rows can
 // reach and stop after the last one; the mask removes the tiles' slack.
@@ -21,11 +21,9 @@
 //   dk / dv : per key tile; per query tile the same P and dS, transposed; dV += P_dropped^T dCtx, dK += dS^T Q.
 //   dtable  : per (head, offset) the slabs summed in a fixed order; then per (bucket, head) the offsets mapped to it, ascending.
 // No atomics anywhere: bitwise reproducible.  Nothing L x L (or L x (2r+1)) ever touches memory.
-#include <algorithm>
-#include "band_common.h"
+#include "attn_tile.h"
 
 #define TT 32            // rows per tile (queries and keys)
-#define TPS (TT + 1)     // LDS row stride (floats) of a 32 x 32 coefficient tile
 #define T5_MAX_RADIUS 1024
 
 struct T5Args {
@@ -41,78 +39,6 @@ struct T5Args {
 // attention-probability dropout: keep decision of (activation row of the query, head, offset j - i)
 __device__ __forceinline__ bool t5_keep(const T5Args& a, int grow, int h, int off) {
   return mts_hash32(a.drop_seed, ((uint64_t)grow * a.heads + h) * (uint64_t)(2 * a.radius + 1) + (uint64_t)(off + a.radius)) >= a.drop_thr;
-}
-
-// rows [first, first + TT) of one head's slice of a row-major [., ld] matrix into LDS; rows outside [0, limit) -> 0
-template <typename T>
-__device__ __forceinline__ void t5_stage(char* dst, int rs, const T* __restrict__ base, int ld, int first, int limit, int hd) {
-  constexpr int VEC = 16 / sizeof(T);
-  const int cpr = hd / VEC;
-  for (int idx = threadIdx.x; idx < TT * cpr; idx += 256) {
-    const int r = idx / cpr, ch = idx % cpr;
-    const int j = first + r;
-    uint4 v = make_uint4(0, 0, 0, 0);
-    if (j >= 0 && j < limit) v = *reinterpret_cast<const uint4*>(base + (size_t)j * ld + ch * VEC);
-    *reinterpret_cast<uint4*>(dst + r * rs + ch * 16) = v;
-  }
-}
-
-__device__ __forceinline__ float t5dot16(const uint4& a, const uint4& b, float acc, float) {
-  acc = fmaf(__uint_as_float(a.x), __uint_as_float(b.x), acc);
-  acc = fmaf(__uint_as_float(a.y), __uint_as_float(b.y), acc);
-  acc = fmaf(__uint_as_float(a.z), __uint_as_float(b.z), acc);
-  acc = fmaf(__uint_as_float(a.w), __uint_as_float(b.w), acc);
-  return acc;
-}
-__device__ __forceinline__ float t5dot16(const uint4& a, const uint4& b, float acc, bf16_t) {
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, a.x), __builtin_bit_cast(bf16x2, b.x), acc, false);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, a.y), __builtin_bit_cast(bf16x2, b.y), acc, false);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, a.z), __builtin_bit_cast(bf16x2, b.z), acc, false);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, a.w), __builtin_bit_cast(bf16x2, b.w), acc, false);
-  return acc;
-}
-
-// s[c] = <A[t, :], B[g + 8c, :]>, c = 0..3
-template <typename T>
-__device__ __forceinline__ void t5_scores(const char* As, const char* Bs, int rs, int hd, int t, int g, float (&s)[4]) {
-  constexpr int VEC = 16 / sizeof(T);
-  const int cpr = hd / VEC;
-  const char* ar = As + t * rs;
-  const char* br = Bs + g * rs;
-  s[0] = s[1] = s[2] = s[3] = 0.f;
-  for (int ch = 0; ch < cpr; ++ch) {
-    const uint4 av = *reinterpret_cast<const uint4*>(ar + ch * 16);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const uint4 bv = *reinterpret_cast<const uint4*>(br + (8 * c) * rs + ch * 16);
-      s[c] = t5dot16(av, bv, s[c], T());
-    }
-  }
-}
-
-// acc[u][0..3] += sum_{c < ncc} coef[c] * Rows[c][4 (g + 8u) ..]   (head dim 64: two chunks of 4 per lane)
-template <typename T>
-__device__ __forceinline__ void t5_accum(const float* coef, const char* Rows, int rs, int g, int ncc, float (&acc)[2][4]) {
-  for (int c = 0; c < ncc; ++c) {
-    const float p = coef[c];
-    const T* row = reinterpret_cast<const T*>(Rows + c * rs);
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      float v[4];
-      load4<T>(row + 4 * (g + 8 * u), v);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc[u][e] = fmaf(p, v[e], acc[u][e]);
-    }
-  }
-}
-
-__device__ __forceinline__ float t8_max(float v) {   // over the 8 lanes of one row
-  v = fmaxf(v, __shfl_xor(v, 1, 64)); v = fmaxf(v, __shfl_xor(v, 2, 64)); v = fmaxf(v, __shfl_xor(v, 4, 64));
-  return v;
-}
-__device__ __forceinline__ float t8_sum(float v) {
-  v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64);
-  return v;
 }
 
 __device__ __forceinline__ void t5_decode(const T5Args& a, int& tile, int& h, int& b) {
@@ -131,7 +57,7 @@ __global__ __launch_bounds__(256) void t5_fwd_kernel(const T5Args a) {
   char* Qs = smem;
   char* KVs = Qs + TT * a.rs;
   float* Ps = reinterpret_cast<float*>(KVs + TT * a.rs);
-  float* bias_s = Ps + TT * TPS;                       // [2r + 1] this head's bias per offset
+  float* bias_s = Ps + TT * PS;                       // [2r + 1] this head's bias per offset
 
   int tile, h, b;
   t5_decode(a, tile, h, b);
@@ -148,14 +74,14 @@ __global__ __launch_bounds__(256) void t5_fwd_kernel(const T5Args a) {
 
   if (i0 < len) {
     for (int d = threadIdx.x; d <= 2 * r; d += 256) bias_s[d] = a.table[(size_t)a.bkt[d] * a.heads + h];
-    t5_stage<T>(Qs, a.rs, qbase, ld, i0, len, hd);
+    attn_stage_rows<T>(Qs, a.rs, qbase, ld, i0, TT, len, hd);
     const int jlo = max(0, i0 - r), jhi = min(len, min(i0 + TT, len) + r);
     for (int j0 = jlo; j0 < jhi; j0 += TT) {
       __syncthreads();                                 // previous tile's readers are done with KVs (first pass: bias_s, Qs are in)
-      t5_stage<T>(KVs, a.rs, qbase + a.inner, ld, j0, jhi, hd);
+      attn_stage_rows<T>(KVs, a.rs, qbase + a.inner, ld, j0, TT, jhi, hd);
       __syncthreads();
       float s[4];
-      t5_scores<T>(Qs, KVs, a.rs, hd, t, g, s);
+      attn_scores<T>(Qs + t * a.rs, KVs + g * a.rs, a.rs, hd, s);
       float mt = -INFINITY;
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
@@ -163,7 +89,7 @@ __global__ __launch_bounds__(256) void t5_fwd_kernel(const T5Args a) {
         s[c] = (i < len && j0 + g + 8 * c < jhi && off >= -r && off <= r) ? s[c] + bias_s[off + r] : -INFINITY;
         mt = fmaxf(mt, s[c]);
       }
-      const float mn = fmaxf(m, t8_max(mt));
+      const float mn = fmaxf(m, lanes8_max(mt));
       const float ms = mn == -INFINITY ? 0.f : mn;     // no key of this row in the tiles so far: p = 0 and nothing to rescale
       const float alpha = __expf(m - ms);
       float ps = 0.f;
@@ -171,18 +97,18 @@ __global__ __launch_bounds__(256) void t5_fwd_kernel(const T5Args a) {
       for (int c = 0; c < 4; ++c) {
         const float p = __expf(s[c] - ms);
         ps += p;
-        Ps[t * TPS + g + 8 * c] = (a.drop_thr && p != 0.f) ? (t5_keep(a, base + i, h, j0 + g + 8 * c - i) ? p * a.drop_scale : 0.f) : p;
+        Ps[t * PS + g + 8 * c] = (a.drop_thr && p != 0.f) ? (t5_keep(a, base + i, h, j0 + g + 8 * c - i) ? p * a.drop_scale : 0.f) : p;
       }
-      l = l * alpha + t8_sum(ps);
+      l = l * alpha + lanes8_sum(ps);
       m = mn;
 #pragma unroll
       for (int u = 0; u < 2; ++u)
 #pragma unroll
         for (int e = 0; e < 4; ++e) acc[u][e] *= alpha;
       __syncthreads();                                 // K scores done: KVs takes V
-      t5_stage<T>(KVs, a.rs, qbase + 2 * a.inner, ld, j0, jhi, hd);
+      attn_stage_rows<T>(KVs, a.rs, qbase + 2 * a.inner, ld, j0, TT, jhi, hd);
       __syncthreads();
-      t5_accum<T>(Ps + t * TPS, KVs, a.rs, g, min(TT, jhi - j0), acc);
+      attn_accum<T, 2>(Ps + t * PS, 1, KVs, a.rs, 64, g, min(TT, jhi - j0), acc);
     }
   }
   if (i >= a.L) return;
@@ -230,7 +156,7 @@ __global__ __launch_bounds__(256) void t5_bwd_q_kernel(const T5Args a) {
   char* Ks = dOs + TT * a.rs;
   char* Vs = Ks + TT * a.rs;
   float* Ps = reinterpret_cast<float*>(Vs + TT * a.rs);
-  float* bias_s = Ps + TT * TPS;
+  float* bias_s = Ps + TT * PS;
   float* dsum = bias_s + (2 * a.radius + 1);           // [2r + 1] this workgroup's diagonal sums of dS
 
   int tile, h, b;
@@ -255,8 +181,8 @@ __global__ __launch_bounds__(256) void t5_bwd_q_kernel(const T5Args a) {
 #pragma unroll
   for (int u = 0; u < 2; ++u) acc[u][0] = acc[u][1] = acc[u][2] = acc[u][3] = 0.f;
   if (i0 < len) {
-    t5_stage<T>(Qs, a.rs, qbase, ld, i0, len, hd);
-    t5_stage<T>(dOs, a.rs, dobase, a.inner, i0, len, hd);   // padded rows' dCtx is never read
+    attn_stage_rows<T>(Qs, a.rs, qbase, ld, i0, TT, len, hd);
+    attn_stage_rows<T>(dOs, a.rs, dobase, a.inner, i0, TT, len, hd);   // padded rows' dCtx is never read
     float delta = 0.f;
     if (qok) {
 #pragma unroll
@@ -268,18 +194,18 @@ __global__ __launch_bounds__(256) void t5_bwd_q_kernel(const T5Args a) {
         for (int e = 0; e < 4; ++e) delta = fmaf(x[e], y[e], delta);
       }
     }
-    delta = t8_sum(delta);
+    delta = lanes8_sum(delta);
     const float lse = qok ? a.lse[(size_t)(base + i) * a.heads + h] : 0.f;
     if (qok && g == 0) a.delta[(size_t)(base + i) * a.heads + h] = delta;
     const int jlo = max(0, i0 - r), jhi = min(len, min(i0 + TT, len) + r);
     for (int j0 = jlo; j0 < jhi; j0 += TT) {
       __syncthreads();
-      t5_stage<T>(Ks, a.rs, qbase + a.inner, ld, j0, jhi, hd);
-      t5_stage<T>(Vs, a.rs, qbase + 2 * a.inner, ld, j0, jhi, hd);
+      attn_stage_rows<T>(Ks, a.rs, qbase + a.inner, ld, j0, TT, jhi, hd);
+      attn_stage_rows<T>(Vs, a.rs, qbase + 2 * a.inner, ld, j0, TT, jhi, hd);
       __syncthreads();
       float s[4], dp[4];
-      t5_scores<T>(Qs, Ks, a.rs, hd, t, g, s);
-      t5_scores<T>(dOs, Vs, a.rs, hd, t, g, dp);
+      attn_scores<T>(Qs + t * a.rs, Ks + g * a.rs, a.rs, hd, s);
+      attn_scores<T>(dOs + t * a.rs, Vs + g * a.rs, a.rs, hd, dp);
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         const int j = j0 + g + 8 * c, off = j - i;
@@ -287,7 +213,7 @@ __global__ __launch_bounds__(256) void t5_bwd_q_kernel(const T5Args a) {
         const float p = in ? __expf(s[c] + bias_s[off + r] - lse) : 0.f;
         float d = dp[c];
         if (a.drop_thr) d = (in && t5_keep(a, base + i, h, off)) ? d * a.drop_scale : 0.f;
-        Ps[t * TPS + g + 8 * c] = p * (d - delta);
+        Ps[t * PS + g + 8 * c] = p * (d - delta);
       }
       __syncthreads();
       // the tile's dS summed along each diagonal: thread q < 63 owns offset j0 - i0 - 31 + q (distinct per thread), rows in order
@@ -297,12 +223,12 @@ __global__ __launch_bounds__(256) void t5_bwd_q_kernel(const T5Args a) {
           float sacc = 0.f;
           for (int tt = 0; tt < TT; ++tt) {
             const int jj = i0 + tt + off - j0;
-            if (jj >= 0 && jj < TT) sacc += Ps[tt * TPS + jj];
+            if (jj >= 0 && jj < TT) sacc += Ps[tt * PS + jj];
           }
           dsum[off + r] += sacc;
         }
       }
-      t5_accum<T>(Ps + t * TPS, Ks, a.rs, g, min(TT, jhi - j0), acc);
+      attn_accum<T, 2>(Ps + t * PS, 1, Ks, a.rs, 64, g, min(TT, jhi - j0), acc);
     }
   }
   __syncthreads();
@@ -325,8 +251,8 @@ __global__ __launch_bounds__(256) void t5_bwd_kv_kernel(const T5Args a) {
   char* Qs = Vs + TT * a.rs;
   char* dOs = Qs + TT * a.rs;
   float* PT = reinterpret_cast<float*>(dOs + TT * a.rs);   // [key][query] dropped probabilities
-  float* ST = PT + TT * TPS;                                // [key][query] dS
-  float* lse_s = ST + TT * TPS;
+  float* ST = PT + TT * PS;                                // [key][query] dS
+  float* lse_s = ST + TT * PS;
   float* del_s = lse_s + TT;
   float* bias_s = del_s + TT;
 
@@ -347,13 +273,13 @@ __global__ __launch_bounds__(256) void t5_bwd_kv_kernel(const T5Args a) {
 
   if (j0 < len) {                                      // padded keys: probability 0, gradient 0
     for (int d = threadIdx.x; d <= 2 * r; d += 256) bias_s[d] = a.table[(size_t)a.bkt[d] * a.heads + h];
-    t5_stage<T>(Ks, a.rs, qbase + a.inner, ld, j0, len, hd);
-    t5_stage<T>(Vs, a.rs, qbase + 2 * a.inner, ld, j0, len, hd);
+    attn_stage_rows<T>(Ks, a.rs, qbase + a.inner, ld, j0, TT, len, hd);
+    attn_stage_rows<T>(Vs, a.rs, qbase + 2 * a.inner, ld, j0, TT, len, hd);
     const int ilo = max(0, j0 - r), ihi = min(len, min(j0 + TT, len) + r);
     for (int q0 = ilo; q0 < ihi; q0 += TT) {
       __syncthreads();
-      t5_stage<T>(Qs, a.rs, qbase, ld, q0, ihi, hd);
-      t5_stage<T>(dOs, a.rs, dobase, a.inner, q0, ihi, hd);
+      attn_stage_rows<T>(Qs, a.rs, qbase, ld, q0, TT, ihi, hd);
+      attn_stage_rows<T>(dOs, a.rs, dobase, a.inner, q0, TT, ihi, hd);
       if (threadIdx.x < TT) {
         const int i = q0 + threadIdx.x;
         const bool ok = i < ihi;
@@ -362,8 +288,8 @@ __global__ __launch_bounds__(256) void t5_bwd_kv_kernel(const T5Args a) {
       }
       __syncthreads();
       float s[4], dp[4];
-      t5_scores<T>(Ks, Qs, a.rs, hd, t, g, s);
-      t5_scores<T>(Vs, dOs, a.rs, hd, t, g, dp);
+      attn_scores<T>(Ks + t * a.rs, Qs + g * a.rs, a.rs, hd, s);
+      attn_scores<T>(Vs + t * a.rs, dOs + g * a.rs, a.rs, hd, dp);
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         const int ci = g + 8 * c, i = q0 + ci, off = j - i;
@@ -371,13 +297,13 @@ __global__ __launch_bounds__(256) void t5_bwd_kv_kernel(const T5Args a) {
         const float p = in ? __expf(s[c] + bias_s[off + r] - lse_s[ci]) : 0.f;
         float keep = 1.f;
         if (a.drop_thr) keep = (in && t5_keep(a, base + i, h, off)) ? a.drop_scale : 0.f;
-        PT[t * TPS + ci] = p * keep;
-        ST[t * TPS + ci] = p * (dp[c] * keep - del_s[ci]);
+        PT[t * PS + ci] = p * keep;
+        ST[t * PS + ci] = p * (dp[c] * keep - del_s[ci]);
       }
       __syncthreads();
       const int ncq = min(TT, ihi - q0);
-      t5_accum<T>(PT + t * TPS, dOs, a.rs, g, ncq, dv);
-      t5_accum<T>(ST + t * TPS, Qs, a.rs, g, ncq, dk);
+      attn_accum<T, 2>(PT + t * PS, 1, dOs, a.rs, 64, g, ncq, dv);
+      attn_accum<T, 2>(ST + t * PS, 1, Qs, a.rs, 64, g, ncq, dk);
     }
   }
   if (j < a.L) {
@@ -422,9 +348,8 @@ __global__ __launch_bounds__(256) void t5_bucket_scatter_kernel(const T5Args a, 
 }
 
 // ------------------------------------------------------------------------------------------------
-// bf16 matrix-core path (head dim 64): v_mfma_f32_16x16x32_bf16, 4 waves x 16 rows per workgroup -- full_attn.hip's matrix-core
-// layout (every product X . Y^T from row-major LDS images; lane l takes row l&15, k-elements 8(l>>4) .. +7 of X and Y; the 16 x 16
-// result sits at [row 4(l>>4) + r][col l&15]) restricted to the band, plus the bias and the padded-row rule.
+// bf16 matrix-core path (head dim 64): v_mfma_f32_16x16x32_bf16, 4 waves x 16 rows per workgroup -- the fragment layout of
+// attn_tile.h (every product X . Y^T from row-major LDS images) restricted to the band, plus the bias and the padded-row rule.
 //   forward : workgroup = 64 queries; per 32-key tile of the band S = Q K^T + bias, online softmax on the C fragments, P (bf16) ->
 //             LDS, ctx += P Vt^T.  Padded rows of the tile: the uniform mean, one thread per (row, 4 dims).
 //   dq      : workgroup = 64 queries; dS (bf16) -> LDS for dQ += dS Kt^T, and in fp32 to a second tile whose 95 diagonals threads
@@ -432,62 +357,9 @@ __global__ __launch_bounds__(256) void t5_bucket_scatter_kernel(const T5Args a, 
 //   dk / dv : workgroup = 64 keys; per 32-query tile of the band S^T = K Q^T, dP^T = V dO^T, dV += P^T dOt^T, dK += dS^T Qt^T.
 // Fixed tiles and loop orders, no atomics: bitwise reproducible.  mts_set_option("t5_mfma", 0) sends bf16 to the generic kernels.
 // ------------------------------------------------------------------------------------------------
-#define MQ 64                   // rows per workgroup
-#define MK 32                   // columns per step
 #define MKK 2                   // 32-wide k-steps of the head dim
 #define MNT 4                   // 16-wide tiles of the head dim
-#define TRS (MK * 2 + 16)       // bytes per row of a transposed [dim][32] image (16-byte aligned, padded)
 #define DSS (MK + 1)            // LDS row stride (floats) of the fp32 dS tile
-
-__device__ __forceinline__ bf16x8 t5m_frag(const char* img, int rs, int row, int col_elem) {
-  return *reinterpret_cast<const bf16x8*>(img + row * rs + col_elem * 2);
-}
-
-// rows [first, first + n) of one head's slice into a row-major image `img` (if any) and / or its transpose timg[d][r] (n <= 32);
-// rows outside [0, limit) -> 0
-__device__ __forceinline__ void t5m_stage(char* img, int rs, char* timg, const bf16_t* __restrict__ base, int ld, int first, int n, int limit) {
-  for (int idx = threadIdx.x; idx < n * 8; idx += 256) {
-    const int r = idx >> 3, ch = idx & 7;
-    const int j = first + r;
-    uint4 v = make_uint4(0, 0, 0, 0);
-    if (j >= 0 && j < limit) v = *reinterpret_cast<const uint4*>(base + (size_t)j * ld + ch * 8);
-    if (img) *reinterpret_cast<uint4*>(img + r * rs + ch * 16) = v;
-    if (timg) {
-      const bf16_t* e = reinterpret_cast<const bf16_t*>(&v);
-#pragma unroll
-      for (int t = 0; t < 8; ++t) *reinterpret_cast<bf16_t*>(timg + (ch * 8 + t) * TRS + r * 2) = e[t];
-    }
-  }
-}
-
-// acc[ct] += X[x0 + 0..15] . Y[16 ct + 0..15]^T over kk k-steps of 32
-template <int NCT>
-__device__ __forceinline__ void t5m_mm(const char* X, int xrs, int x0, const char* Y, int yrs, int kk, int lane, f32x4 (&acc)[NCT]) {
-  const int l15 = lane & 15, g = lane >> 4;
-  for (int k = 0; k < kk; ++k) {
-    const bf16x8 a = t5m_frag(X, xrs, x0 + l15, 32 * k + 8 * g);
-#pragma unroll
-    for (int ct = 0; ct < NCT; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, t5m_frag(Y, yrs, 16 * ct + l15, 32 * k + 8 * g), acc[ct], 0, 0, 0);
-  }
-}
-
-// 16 x 32 coefficient tile (C layout, two 16-column halves) -> bf16 image W[16][32] of this wave (row stride TRS)
-__device__ __forceinline__ void t5m_put(char* W, int lane, const float (&c)[2][4]) {
-  const int l15 = lane & 15, g = lane >> 4;
-#pragma unroll
-  for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) *reinterpret_cast<bf16_t*>(W + (4 * g + r) * TRS + (16 * ct + l15) * 2) = (bf16_t)c[ct][r];
-}
-
-__device__ __forceinline__ float t16_max(float v) {   // over the 16 lanes that hold one row of a C fragment
-  v = fmaxf(v, __shfl_xor(v, 1, 64)); v = fmaxf(v, __shfl_xor(v, 2, 64)); v = fmaxf(v, __shfl_xor(v, 4, 64)); v = fmaxf(v, __shfl_xor(v, 8, 64));
-  return v;
-}
-__device__ __forceinline__ float t16_sum(float v) {
-  v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64); v += __shfl_xor(v, 8, 64);
-  return v;
-}
 
 // padded query rows [first, end) of document b (activation rows base + i), head h: the uniform mean of their three blocks of r + 1
 // rows of v, j in order; one thread per (row, 4 dims)
@@ -529,8 +401,8 @@ __global__ __launch_bounds__(256) void t5m_fwd_kernel(const T5Args a) {
   char* W = Pw + w * 16 * TRS;
   if (q0 < len) {
     for (int d = threadIdx.x; d <= 2 * r; d += 256) bias_s[d] = a.table[(size_t)a.bkt[d] * a.heads + h];
-    t5m_stage(Qs, a.rs, nullptr, qbase, ld, q0, MQ / 2, len);
-    t5m_stage(Qs + (MQ / 2) * a.rs, a.rs, nullptr, qbase, ld, q0 + MQ / 2, MQ / 2, len);
+    attn_mstage(Qs, a.rs, nullptr, qbase, ld, q0, MQ / 2, len, 64);
+    attn_mstage(Qs + (MQ / 2) * a.rs, a.rs, nullptr, qbase, ld, q0 + MQ / 2, MQ / 2, len, 64);
     float m[4], l[4];
     f32x4 acc[MNT];
 #pragma unroll
@@ -540,11 +412,11 @@ __global__ __launch_bounds__(256) void t5m_fwd_kernel(const T5Args a) {
     const int jlo = max(0, q0 - r), jhi = min(len, min(q0 + MQ, len) + r);
     for (int j0 = jlo; j0 < jhi; j0 += MK) {
       __syncthreads();                               // previous step's readers are done with Ks / Vt (first pass: bias_s, Qs are in)
-      t5m_stage(Ks, a.rs, nullptr, qbase + a.inner, ld, j0, MK, jhi);
-      t5m_stage(nullptr, 0, Vt, qbase + 2 * a.inner, ld, j0, MK, jhi);
+      attn_mstage(Ks, a.rs, nullptr, qbase + a.inner, ld, j0, MK, jhi, 64);
+      attn_mstage(nullptr, 0, Vt, qbase + 2 * a.inner, ld, j0, MK, jhi, 64);
       __syncthreads();
       f32x4 s[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-      t5m_mm<2>(Qs, a.rs, 16 * w, Ks, a.rs, MKK, lane, s);
+      attn_mm_xyt<2>(Qs, a.rs, 16 * w, Ks, a.rs, MKK, lane, s);
       float p[2][4], alpha[4];
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
@@ -556,7 +428,7 @@ __global__ __launch_bounds__(256) void t5m_fwd_kernel(const T5Args a) {
           s[ct][q] = (i < len && j < jhi && off >= -r && off <= r) ? s[ct][q] + bias_s[off + r] : -INFINITY;
           mt = fmaxf(mt, s[ct][q]);
         }
-        const float mn = fmaxf(m[q], t16_max(mt));
+        const float mn = fmaxf(m[q], lanes16_max(mt));
         const float ms = mn == -INFINITY ? 0.f : mn;   // no key of this row so far: p = 0 and nothing to rescale
         alpha[q] = __expf(m[q] - ms);
         float ps = 0.f;
@@ -567,16 +439,16 @@ __global__ __launch_bounds__(256) void t5m_fwd_kernel(const T5Args a) {
           const int off = j0 + 16 * ct + l15 - i;
           p[ct][q] = (a.drop_thr && e != 0.f) ? (t5_keep(a, base + i, h, off) ? e * a.drop_scale : 0.f) : e;
         }
-        l[q] = l[q] * alpha[q] + t16_sum(ps);
+        l[q] = l[q] * alpha[q] + lanes16_sum(ps);
         m[q] = mn;
       }
 #pragma unroll
       for (int n = 0; n < MNT; ++n)
 #pragma unroll
         for (int q = 0; q < 4; ++q) acc[n][q] *= alpha[q];
-      t5m_put(W, lane, p);
+      attn_put_coef(W, lane, p);
       __syncthreads();
-      t5m_mm<MNT>(W, TRS, 0, Vt, TRS, 1, lane, acc);
+      attn_mm_xyt<MNT>(W, TRS, 0, Vt, TRS, 1, lane, acc);
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -626,10 +498,10 @@ __global__ __launch_bounds__(256) void t5m_bwd_q_kernel(const T5Args a) {
 #pragma unroll
   for (int n = 0; n < MNT; ++n) acc[n] = f32x4{0.f, 0.f, 0.f, 0.f};
   if (q0 < len) {
-    t5m_stage(Qs, a.rs, nullptr, qbase, ld, q0, MQ / 2, len);
-    t5m_stage(Qs + (MQ / 2) * a.rs, a.rs, nullptr, qbase, ld, q0 + MQ / 2, MQ / 2, len);
-    t5m_stage(dOs, a.rs, nullptr, dobase, a.inner, q0, MQ / 2, len);              // padded rows' dCtx is never read
-    t5m_stage(dOs + (MQ / 2) * a.rs, a.rs, nullptr, dobase, a.inner, q0 + MQ / 2, MQ / 2, len);
+    attn_mstage(Qs, a.rs, nullptr, qbase, ld, q0, MQ / 2, len, 64);
+    attn_mstage(Qs + (MQ / 2) * a.rs, a.rs, nullptr, qbase, ld, q0 + MQ / 2, MQ / 2, len, 64);
+    attn_mstage(dOs, a.rs, nullptr, dobase, a.inner, q0, MQ / 2, len, 64);              // padded rows' dCtx is never read
+    attn_mstage(dOs + (MQ / 2) * a.rs, a.rs, nullptr, dobase, a.inner, q0 + MQ / 2, MQ / 2, len, 64);
     if (threadIdx.x < MQ) {                          // delta = dCtx . ctx (fixed order) and lse of valid rows
       const int i = q0 + threadIdx.x;
       float dl = 0.f, lv = 0.f;
@@ -650,13 +522,13 @@ __global__ __launch_bounds__(256) void t5m_bwd_q_kernel(const T5Args a) {
     const int jlo = max(0, q0 - r), jhi = min(len, min(q0 + MQ, len) + r);
     for (int j0 = jlo; j0 < jhi; j0 += MK) {
       __syncthreads();
-      t5m_stage(Ks, a.rs, Kt, qbase + a.inner, ld, j0, MK, jhi);
-      t5m_stage(Vs, a.rs, nullptr, qbase + 2 * a.inner, ld, j0, MK, jhi);
+      attn_mstage(Ks, a.rs, Kt, qbase + a.inner, ld, j0, MK, jhi, 64);
+      attn_mstage(Vs, a.rs, nullptr, qbase + 2 * a.inner, ld, j0, MK, jhi, 64);
       __syncthreads();
       f32x4 s[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
       f32x4 dp[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-      t5m_mm<2>(Qs, a.rs, 16 * w, Ks, a.rs, MKK, lane, s);
-      t5m_mm<2>(dOs, a.rs, 16 * w, Vs, a.rs, MKK, lane, dp);
+      attn_mm_xyt<2>(Qs, a.rs, 16 * w, Ks, a.rs, MKK, lane, s);
+      attn_mm_xyt<2>(dOs, a.rs, 16 * w, Vs, a.rs, MKK, lane, dp);
       float ds[2][4];
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
@@ -672,7 +544,7 @@ __global__ __launch_bounds__(256) void t5m_bwd_q_kernel(const T5Args a) {
           DS[ri * DSS + 16 * ct + l15] = ds[ct][q];
         }
       }
-      t5m_put(W, lane, ds);
+      attn_put_coef(W, lane, ds);
       __syncthreads();
       // the step's dS summed along each diagonal: thread q < 95 owns offset j0 - q0 - 63 + q (distinct per thread), rows in order
       if (threadIdx.x < MQ + MK - 1) {
@@ -686,7 +558,7 @@ __global__ __launch_bounds__(256) void t5m_bwd_q_kernel(const T5Args a) {
           dsum[off + r] += sacc;
         }
       }
-      t5m_mm<MNT>(W, TRS, 0, Kt, TRS, 1, lane, acc);
+      attn_mm_xyt<MNT>(W, TRS, 0, Kt, TRS, 1, lane, acc);
     }
   }
   __syncthreads();
@@ -729,17 +601,17 @@ __global__ __launch_bounds__(256) void t5m_bwd_kv_kernel(const T5Args a) {
   for (int n = 0; n < MNT; ++n) dk[n] = dv[n] = f32x4{0.f, 0.f, 0.f, 0.f};
   if (k0 < len) {                                    // padded keys: gradient 0
     for (int d = threadIdx.x; d <= 2 * r; d += 256) bias_s[d] = a.table[(size_t)a.bkt[d] * a.heads + h];
-    t5m_stage(Ks, a.rs, nullptr, qbase + a.inner, ld, k0, MQ / 2, len);
-    t5m_stage(Ks + (MQ / 2) * a.rs, a.rs, nullptr, qbase + a.inner, ld, k0 + MQ / 2, MQ / 2, len);
-    t5m_stage(Vs, a.rs, nullptr, qbase + 2 * a.inner, ld, k0, MQ / 2, len);
-    t5m_stage(Vs + (MQ / 2) * a.rs, a.rs, nullptr, qbase + 2 * a.inner, ld, k0 + MQ / 2, MQ / 2, len);
+    attn_mstage(Ks, a.rs, nullptr, qbase + a.inner, ld, k0, MQ / 2, len, 64);
+    attn_mstage(Ks + (MQ / 2) * a.rs, a.rs, nullptr, qbase + a.inner, ld, k0 + MQ / 2, MQ / 2, len, 64);
+    attn_mstage(Vs, a.rs, nullptr, qbase + 2 * a.inner, ld, k0, MQ / 2, len, 64);
+    attn_mstage(Vs + (MQ / 2) * a.rs, a.rs, nullptr, qbase + 2 * a.inner, ld, k0 + MQ / 2, MQ / 2, len, 64);
     char* PW = Pw + w * 16 * TRS;
     char* SW = Sw + w * 16 * TRS;
     const int ilo = max(0, k0 - r), ihi = min(len, min(k0 + MQ, len) + r);
     for (int i0 = ilo; i0 < ihi; i0 += MK) {
       __syncthreads();
-      t5m_stage(Qs, a.rs, Qt, qbase, ld, i0, MK, ihi);
-      t5m_stage(dOs, a.rs, dOt, dobase, a.inner, i0, MK, ihi);
+      attn_mstage(Qs, a.rs, Qt, qbase, ld, i0, MK, ihi, 64);
+      attn_mstage(dOs, a.rs, dOt, dobase, a.inner, i0, MK, ihi, 64);
       if (threadIdx.x < MK) {
         const int i = i0 + threadIdx.x;
         const bool ok = i < ihi;
@@ -749,8 +621,8 @@ __global__ __launch_bounds__(256) void t5m_bwd_kv_kernel(const T5Args a) {
       __syncthreads();
       f32x4 s[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
       f32x4 dp[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-      t5m_mm<2>(Ks, a.rs, 16 * w, Qs, a.rs, MKK, lane, s);      // S^T: rows = keys, columns = queries
-      t5m_mm<2>(Vs, a.rs, 16 * w, dOs, a.rs, MKK, lane, dp);    // dP^T
+      attn_mm_xyt<2>(Ks, a.rs, 16 * w, Qs, a.rs, MKK, lane, s);      // S^T: rows = keys, columns = queries
+      attn_mm_xyt<2>(Vs, a.rs, 16 * w, dOs, a.rs, MKK, lane, dp);    // dP^T
       float pt[2][4], st[2][4];
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
@@ -766,11 +638,11 @@ __global__ __launch_bounds__(256) void t5m_bwd_kv_kernel(const T5Args a) {
           st[ct][q] = p * (dp[ct][q] * keep - del_s[ci]);
         }
       }
-      t5m_put(PW, lane, pt);
-      t5m_put(SW, lane, st);
+      attn_put_coef(PW, lane, pt);
+      attn_put_coef(SW, lane, st);
       __syncthreads();
-      t5m_mm<MNT>(PW, TRS, 0, dOt, TRS, 1, lane, dv);
-      t5m_mm<MNT>(SW, TRS, 0, Qt, TRS, 1, lane, dk);
+      attn_mm_xyt<MNT>(PW, TRS, 0, dOt, TRS, 1, lane, dv);
+      attn_mm_xyt<MNT>(SW, TRS, 0, Qt, TRS, 1, lane, dk);
     }
   }
 #pragma unroll
@@ -790,12 +662,6 @@ __global__ __launch_bounds__(256) void t5m_bwd_kv_kernel(const T5Args a) {
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-static int t5_row_stride(int hd, int esize) {
-  int bytes = ((hd * esize + 15) / 16) * 16;
-  if (((bytes / 16) & 1) == 0) bytes += 16;   // 16 B x odd: the rows of one column hit distinct 16-byte bank slots
-  return bytes;
-}
-
 static int t5_fill(T5Args& a, int dtype, int B, int L, int heads, int head_dim, int radius, int buckets, const char* who) {
   MTS_CHECK_ARG(B > 0 && L > 0 && heads > 0 && radius >= 1 && buckets >= 1, "%s: bad shape", who);
   MTS_CHECK_ARG(dtype == MTS_F32 || dtype == MTS_BF16, "%s: bad dtype %d", who, dtype);
@@ -804,26 +670,16 @@ static int t5_fill(T5Args& a, int dtype, int B, int L, int heads, int head_dim, 
   MTS_UNSUPPORTED((long)B * L * heads * 64 * 3 < (1L << 31), "%s: problem too large for 32-bit row indexing", who);
   memset(&a, 0, sizeof(a));
   a.B = B; a.L = L; a.heads = heads; a.hd = head_dim; a.inner = heads * head_dim; a.radius = radius; a.buckets = buckets;
-  a.rs = t5_row_stride(head_dim, dtype == MTS_F32 ? 4 : 2);
+  a.rs = attn_row_stride(head_dim, dtype == MTS_F32 ? 4 : 2);
   a.drop_scale = 1.f;
   return MTS_OK;
 }
 
-static int t5_set_dropout(T5Args& a, float p, uint64_t seed, const char* who) {
-  MTS_CHECK_ARG(p >= 0.f && p < 1.f, "%s: dropout probability has to be between 0 and 1, but got %f", who, (double)p);
-  if (p > 0.f) {
-    a.drop_thr = (uint32_t)std::max<double>(1.0, std::min<double>(4294967295.0, (double)p * 4294967296.0));
-    a.drop_scale = 1.0f / (1.0f - p);
-    a.drop_seed = seed;
-  }
-  return MTS_OK;
-}
-
 // LDS of the generic kernels (at most 56 KiB at the largest radius: no attribute call needed)
-static size_t t5_fwd_lds(const T5Args& a) { return (size_t)2 * TT * a.rs + (size_t)(TT * TPS + 2 * a.radius + 1) * sizeof(float); }
-static size_t t5_bwd_q_lds(const T5Args& a) { return (size_t)4 * TT * a.rs + (size_t)(TT * TPS + 2 * (2 * a.radius + 1)) * sizeof(float); }
+static size_t t5_fwd_lds(const T5Args& a) { return (size_t)2 * TT * a.rs + (size_t)(TT * PS + 2 * a.radius + 1) * sizeof(float); }
+static size_t t5_bwd_q_lds(const T5Args& a) { return (size_t)4 * TT * a.rs + (size_t)(TT * PS + 2 * (2 * a.radius + 1)) * sizeof(float); }
 static size_t t5_bwd_kv_lds(const T5Args& a) {
-  return (size_t)4 * TT * a.rs + (size_t)(2 * TT * TPS + 2 * TT + 2 * a.radius + 1) * sizeof(float);
+  return (size_t)4 * TT * a.rs + (size_t)(2 * TT * PS + 2 * TT + 2 * a.radius + 1) * sizeof(float);
 }
 
 // matrix-core kernels (bf16): at most 62 KiB at the largest radius
@@ -853,7 +709,7 @@ extern "C" int mts_t5_local_attn_fwd(void* stream, int dtype, int B, int L, int 
   if (rc) return rc;
   MTS_CHECK_ARG(qkv && table && bucket_of_offset && ctx && lse, "mts_t5_local_attn_fwd: null pointer");
   MTS_UNSUPPORTED(t5_aligned16(qkv) && t5_aligned16(ctx), "mts_t5_local_attn_fwd: qkv and ctx must be 16-byte aligned");
-  rc = t5_set_dropout(a, drop_p, drop_seed, "mts_t5_local_attn_fwd");
+  rc = attn_set_dropout(a, drop_p, drop_seed, "mts_t5_local_attn_fwd");
   if (rc) return rc;
   a.qkv = qkv; a.lengths = lengths; a.table = table; a.bkt = bucket_of_offset; a.ctx = ctx; a.lse = lse;
   if (t5_use_mfma(a, dtype)) {
@@ -886,7 +742,7 @@ extern "C" int mts_t5_local_attn_bwd(void* stream, int dtype, int B, int L, int 
                 "mts_t5_local_attn_bwd: null pointer (workspace is required)");
   MTS_UNSUPPORTED(t5_aligned16(qkv) && t5_aligned16(ctx) && t5_aligned16(dctx) && t5_aligned16(dqkv),
                   "mts_t5_local_attn_bwd: qkv, ctx, dctx and dqkv must be 16-byte aligned");
-  rc = t5_set_dropout(a, drop_p, drop_seed, "mts_t5_local_attn_bwd");
+  rc = attn_set_dropout(a, drop_p, drop_seed, "mts_t5_local_attn_bwd");
   if (rc) return rc;
   a.qkv = qkv; a.lengths = lengths; a.table = table; a.bkt = bucket_of_offset; a.lse = const_cast<float*>(lse);
   a.ctx = const_cast<void*>(ctx); a.dctx = dctx; a.dqkv = dqkv;
