@@ -402,6 +402,33 @@ int mts_head_bwd_data(void* stream, int dtype, int rows, int D, int n_out, const
                       void* dx, int lddx, int accumulate);
 
 /* ---------------------------------------------------------------------------------------------
+ * Domain-switched heads.  Replaces the `switch == 'dense'` tail of SwitchBiLSTM (models/CRF.py:1195-1205 in loss, :1248-1258 in
+ * forward) with its regroup (:1132-1139): classification_1 / classification_2 over the whole batch and the per-document pick.
+ * x, dx: [B*L, D] act dtype with leading dimensions in ELEMENTS; w: fp32 [2, n_out, D] (the two heads stacked), bias: fp32 [2, n_out];
+ * n_out in 1..4; scores, dscores: fp32 [B, L, n_out].  int32 device maps, built on the host from the batch's `domains`:
+ *   doc_head [B]: the head (0 = classification_1, 1 = classification_2) that scores document b;
+ *   doc_src  [B]: the document whose rows of x document b is scored from (upstream: its rank inside its own domain group);
+ *   doc_tgt  [2, B]: doc_tgt[k][r] = the one document of head k with doc_src == r, or -1 (the inverse of the two maps above).
+ * forward:    scores[b, t, c] = x[doc_src[b], t, :] . w[doc_head[b], c, :] + bias[doc_head[b], c]   (fp32 accumulation)
+ * bwd_params: dw[k, c, :] = sum_{b: doc_head[b] = k} sum_t dscores[b, t, c] x[doc_src[b], t, :], db[k, c] likewise; OVERWRITE: a head that
+ *             no document uses comes out as exact zeros; no atomics, bitwise reproducible.  workspace: mts_switch_head_bwd_workspace(D)
+ *             bytes, 16-byte aligned.
+ * bwd_data:   dx[r, t, :] = sum_k sum_c dscores[doc_tgt[k][r], t, c] w[k, c, :]  (gather form, no atomics); every row is OVERWRITTEN, rows
+ *             that no document reads with zeros.
+ * A map entry outside its range (doc_src not in [0, B), doc_head not in {0, 1}, doc_tgt not in [-1, B)) contributes nothing: the
+ * kernels write 0 there and form no address from it.
+ * MTS_ERR_INVALID before any launch: D or a leading dimension no multiple of 4; x / dx not aligned to a 4-element vector (16 bytes in
+ * fp32, 8 in bf16); w, dw or the workspace not 16-byte aligned; n_out outside 1..4.  MTS_ERR_UNSUPPORTED: bwd_params with D > 4096.
+ * ------------------------------------------------------------------------------------------- */
+int mts_switch_head_fwd(void* stream, int dtype, int B, int L, int D, int n_out, const void* x, int ldx, const float* w,
+                        const float* bias, const int32_t* doc_src, const int32_t* doc_head, float* scores);
+size_t mts_switch_head_bwd_workspace(int D);
+int mts_switch_head_bwd_params(void* stream, int dtype, int B, int L, int D, int n_out, const void* x, int ldx, const float* dscores,
+                               const int32_t* doc_src, const int32_t* doc_head, float* dw, float* db, void* workspace);
+int mts_switch_head_bwd_data(void* stream, int dtype, int B, int L, int D, int n_out, const float* dscores, const float* w,
+                             const int32_t* doc_tgt, void* dx, int lddx);
+
+/* ---------------------------------------------------------------------------------------------
  * LSTM recurrence with packed-sequence semantics.
  * Replaces: aten::lstm under pack_padded_sequence / pad_packed_sequence
  * (models/NeuralArchitectures.py:98-115): gate order i,f,g,o, zero initial state, rows >= len are 0,

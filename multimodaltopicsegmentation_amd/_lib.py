@@ -96,6 +96,10 @@ SIGNATURES = {
     'mts_head_fwd': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     'mts_head_bwd_params': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     'mts_head_bwd_data': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i]),
+    'mts_switch_head_fwd': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    'mts_switch_head_bwd_workspace': (_sz, [_i]),
+    'mts_switch_head_bwd_params': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'mts_switch_head_bwd_data': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i]),
     'mts_lstm_workspace': (_sz, [_i, _i, _i, _i, _i]),
     'mts_lstm_fwd': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'mts_lstm_bwd': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

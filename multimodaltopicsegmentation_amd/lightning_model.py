@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 
 from . import metrics
-from .rnn_taggers import BiLSTM, BiLSTMLateFusion, BiRnnCrf, SheikhBiLSTM
+from .rnn_taggers import BiLSTM, BiLSTMLateFusion, BiRnnCrf, SheikhBiLSTM, SwitchBiLSTM
 from .t5_taggers import RecurrentLongT5
 from .taggers import Transformer_segmenter
 
@@ -43,7 +43,7 @@ except Exception:  # noqa: BLE001
             return obj
 
 # architectures of the reference that are outside the hot path
-_OUT_OF_SCOPE = ('SimpleBiLSTM', 'MLP', 'Transformer-CRF', 'BiLSTMRestrictedMHA', 'SwitchBiLSTM')
+_OUT_OF_SCOPE = ('SimpleBiLSTM', 'MLP', 'Transformer-CRF', 'BiLSTMRestrictedMHA')
 
 
 class TextSegmenter(_Base):
@@ -94,9 +94,17 @@ class TextSegmenter(_Base):
             # the user's dropout_in, loss_fn, threshold, alpha and gamma are not passed on
             self.model = SheikhBiLSTM(tagset_size, embedding_dim, hidden_dim, num_layers=num_layers, dropout_in=0.5, dropout_attention=0,
                                       batch_first=True, compute_dtype=compute_dtype)
-        elif architecture in _OUT_OF_SCOPE:
-            if architecture == 'SwitchBiLSTM' and switch == 'bias':
+        elif architecture == 'SwitchBiLSTM':
+            # lightning_model.py:224-243: 'lstm' -> two encoders, 'dense' -> two heads, 'bias' is refused, any other string leaves both
+            # flags off (a plain BiLSTM that still takes the batch's domains)
+            if switch == 'bias':
                 raise NotImplementedError()                                  # lightning_model.py:235
+            self.model = SwitchBiLSTM(tagset_size, embedding_dim, hidden_dim, num_layers=num_layers, bidirectional=bidirectional,
+                                      dropout_in=dropout_in, dropout_out=dropout_out, batch_first=batch_first, LSTM=LSTM, loss_fn=loss_fn,
+                                      threshold=threshold, alpha=alpha, gamma=gamma, bias_adapt=False, switch_lstm_adapt=switch == 'lstm',
+                                      switch_dense_adapt=switch == 'dense', compute_dtype=compute_dtype)
+            self.domain = True
+        elif architecture in _OUT_OF_SCOPE:
             raise NotImplementedError(f"architecture '{architecture}' exists in the reference but is outside the accelerated "
                                       'hot path (SURVEY.md §2/§8f)')
         else:
@@ -130,7 +138,13 @@ class TextSegmenter(_Base):
         sentence, target, lengths = self._sentence(batch), batch['tgt_tokens'], batch['src_lengths']
         segments = batch['src_segments'] if self.cos else None
         self.best_th, self.losses, self.targets = [], [], []
-        if self.double_input:
+        if self.domain:
+            domain = batch['domain']
+            try:
+                loss = self.model.loss(sentence, lengths, target, domain, segments=segments)
+            except TypeError:
+                loss = self.model.loss(sentence, lengths, target, domain)
+        elif self.double_input:
             sentence2 = batch['src_tokens2']
             try:
                 loss = self.model.loss(sentence, sentence2, lengths, target, segments=segments)
@@ -148,7 +162,9 @@ class TextSegmenter(_Base):
     def validation_step(self, batch, batch_idx):
         sentence, target, lengths = self._sentence(batch), batch['tgt_tokens'], batch['src_lengths']
         if self.s_th:
-            if self.double_input:
+            if self.domain:
+                scores, tags = self.model(sentence, lengths, batch['domain'])
+            elif self.double_input:
                 scores, tags = self.model(sentence, batch['src_tokens2'], lengths)
             else:
                 scores, tags = self.model(sentence, lengths)
@@ -157,7 +173,9 @@ class TextSegmenter(_Base):
                 self.targets.append(target[index][:lengths[index]].detach().cpu().numpy())
             return None
         with torch.no_grad():
-            if self.double_input:
+            if self.domain:
+                loss = self.model.loss(sentence, lengths, target, batch['domain'])
+            elif self.double_input:
                 loss = self.model.loss(sentence, batch['src_tokens2'], lengths, target)
             else:
                 loss = self.model.loss(sentence, lengths, target)
@@ -178,7 +196,9 @@ class TextSegmenter(_Base):
             if not threshold:
                 threshold = 0.5
             self.model.th = threshold
-            if self.double_input:
+            if self.domain:
+                score, tags = self.model(sentence, lengths, batch['domain'])
+            elif self.double_input:
                 score, tags = self.model(sentence, batch['src_tokens2'], lengths)
             else:
                 score, tags = self.model(sentence, lengths)
@@ -224,6 +244,10 @@ class TextSegmenter(_Base):
         if getattr(self, 'double_input', False) and batch.get('src_tokens2') is not None:
             # the reference calls model(sentence, lengths) here and raises TypeError for late-fusion models; serve them instead
             score, tags = self.model(batch['src_tokens'], batch['src_tokens2'], batch['src_lengths'])
+        elif getattr(self, 'domain', False) and batch.get('domain') is not None:
+            # the same decision for a domain model: upstream's model(sentence, lengths) raises TypeError (`domains` is missing); a batch
+            # that carries 'domain' is served, one that does not raises that TypeError below
+            score, tags = self.model(self._sentence(batch), batch['src_lengths'], batch['domain'])
         else:
             score, tags = self.model(self._sentence(batch), batch['src_lengths'])
         return tags

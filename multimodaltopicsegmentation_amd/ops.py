@@ -423,6 +423,98 @@ def head_bwd_data(dscores, w, dx, accumulate=False):
                                 dx.stride(0), int(accumulate)))
 
 
+def switch_doc_maps(domains, B=None):
+    """Host side of the domain-switched heads (include/mts.h): the three document maps of a batch's ``domains`` as int lists.
+
+    models/CRF.py:1124-1139: idx1 = the documents whose domain is truthy (head 0 = classification_1), idx2 = the rest (head 1 =
+    classification_2), both in batch order; ``regroup`` writes out[idx1[k]] = head_1(h)[k] and out[idx2[k]] = head_2(h)[k], so document
+    i is scored from the encoder rows of document rank(i), its position inside its own group.  On a single-domain batch rank(i) = i.
+    -> (doc_src [B], doc_head [B], doc_tgt [2 * B] = for head k and document r the one document of head k that reads r, or -1).
+    ValueError for anything that is not a sequence of B entries, each 0 / 1 / a bool."""
+    if isinstance(domains, torch.Tensor):
+        domains = domains.tolist()
+    if isinstance(domains, (str, bytes)) or not hasattr(domains, '__len__') or not hasattr(domains, '__iter__'):
+        raise ValueError(f'domains must be a sequence of 0 / 1 / bool, one per document; got {type(domains).__name__}')
+    doms = list(domains)
+    if B is not None and len(doms) != B:
+        raise ValueError(f'domains has {len(doms)} entries for a batch of {B} documents')
+    for d in doms:
+        if isinstance(d, bool) or (hasattr(d, '__index__') and not isinstance(d, float) and int(d) in (0, 1)):
+            continue
+        raise ValueError(f'domains entries must be 0, 1 or a bool; got {d!r}')
+    n = len(doms)
+    src, head, tgt = [0] * n, [0] * n, [-1] * (2 * n)
+    rank = [0, 0]
+    for i, d in enumerate(doms):
+        k = 0 if d else 1
+        src[i], head[i] = rank[k], k
+        tgt[k * n + rank[k]] = i
+        rank[k] += 1
+    return src, head, tgt
+
+
+_SWITCH_MAPS_CACHE = {}
+
+
+def switch_maps(domains, B, device):
+    """switch_doc_maps on the device (int32): one small upload per distinct (domains, device), none per step."""
+    if isinstance(domains, torch.Tensor):
+        domains = domains.tolist()
+    try:
+        key = (tuple((type(d), d) for d in domains), int(B), str(torch.device(device)))
+        hit = _SWITCH_MAPS_CACHE.get(key)
+    except TypeError:
+        key = hit = None
+    if hit is None:
+        src, head, tgt = switch_doc_maps(domains, B)
+        up = torch.tensor([src, head, tgt[:B], tgt[B:]], dtype=torch.int32).reshape(4, B).to(device)
+        hit = (up[0], up[1], up[2:].reshape(-1))
+        if key is not None:
+            if len(_SWITCH_MAPS_CACHE) > 64:
+                _SWITCH_MAPS_CACHE.clear()
+            _SWITCH_MAPS_CACHE[key] = hit
+    return hit
+
+
+def _switch_check(who, act, B, Lq, w):
+    """The operands mts_switch_head_* does not cover, refused here as ValueError before anything is launched."""
+    rows, D = act.shape
+    if rows != B * Lq:
+        raise ValueError(f'{who}: {rows} rows for a batch of {B} x {Lq}')
+    if D % 4 or act.stride(0) % 4 or act.stride(1) != 1:
+        raise ValueError(f'{who}: D = {D} and the row stride {act.stride(0)} must be multiples of 4 (4-element vectors), columns contiguous')
+    if act.data_ptr() % (4 * act.element_size()):
+        raise ValueError(f'{who}: the {act.dtype} operand must be aligned to a 4-element vector ({4 * act.element_size()} bytes)')
+    if w.dim() != 3 or w.shape[0] != 2 or not 1 <= w.shape[1] <= 4 or w.shape[2] != D or not w.is_contiguous() or w.dtype != torch.float32:
+        raise ValueError(f'{who}: head weights must be contiguous fp32 [2, n_out <= 4, {D}], got {tuple(w.shape)}')
+
+
+def switch_head_fwd(x, w, b, domains, B, Lq, scores):
+    """scores[b, t, c] = x[doc_src[b], t, :] . w[doc_head[b], c, :] + b[doc_head[b], c] (include/mts.h).  x: [B*Lq, D] act dtype (row
+    stride free), w fp32 [2, n_out, D], b fp32 [2, n_out], domains: the batch's host list, scores fp32 [B*Lq, n_out]."""
+    _switch_check('switch_head_fwd', x, B, Lq, w)
+    src, head, _ = switch_maps(domains, B, x.device)
+    check(lib.mts_switch_head_fwd(stream_ptr(), dtype_code(x.dtype), B, Lq, x.shape[1], w.shape[1], ptr(x), x.stride(0), ptr(w), ptr(b),
+                                  ptr(src), ptr(head), ptr(scores)))
+
+
+def switch_head_bwd_params(x, dscores, domains, B, Lq, dw, db):
+    """dw fp32 [2, n_out, D], db fp32 [2, n_out]: OVERWRITTEN; the head no document uses with exact zeros."""
+    _switch_check('switch_head_bwd_params', x, B, Lq, dw)
+    src, head, _ = switch_maps(domains, B, x.device)
+    ws = _scratch(lib.mts_switch_head_bwd_workspace(x.shape[1]), x.device, 'switch_bwd')
+    check(lib.mts_switch_head_bwd_params(stream_ptr(), dtype_code(x.dtype), B, Lq, x.shape[1], dw.shape[1], ptr(x), x.stride(0), ptr(dscores),
+                                         ptr(src), ptr(head), ptr(dw), ptr(db), ptr(ws)))
+
+
+def switch_head_bwd_data(dscores, w, domains, B, Lq, dx):
+    """dx[r, t, :] = sum_k sum_c dscores[doc_tgt[k][r], t, c] w[k, c, :]: every row OVERWRITTEN, rows no document reads with zeros."""
+    _switch_check('switch_head_bwd_data', dx, B, Lq, w)
+    _, _, tgt = switch_maps(domains, B, dx.device)
+    check(lib.mts_switch_head_bwd_data(stream_ptr(), dtype_code(dx.dtype), B, Lq, dx.shape[1], w.shape[1], ptr(dscores), ptr(w), ptr(tgt),
+                                       ptr(dx), dx.stride(0)))
+
+
 def lstm_workspace(dtype, B, Lq, H, ndir, device, tag='lstm'):
     return _scratch(lib.mts_lstm_workspace(dtype_code(dtype), B, Lq, H, ndir), device, tag)
 

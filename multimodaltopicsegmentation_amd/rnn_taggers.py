@@ -694,3 +694,156 @@ class SheikhBiLSTM(_RnnTaggerBase):
             L.check_async()
             lens = [int(v) for v in (lenghts.tolist() if lenghts is not None else [Lq] * B)]
         return scores, [tags_h[i, :lens[i]].tolist() for i in range(B)]
+
+
+class SwitchBiLSTM(_RnnTaggerBase):
+    """models/CRF.py:1046-1270: the domain-adaptation BiLSTM.  ``domains`` (one 0 / 1 / bool per document, the collater's
+    ``batch['domain']``) picks, per document, one of two heads (``switch_dense_adapt``: 'dense') or, per batch, one of two encoders
+    (``switch_lstm_adapt``: 'lstm'); with neither flag this is ``BiLSTM`` (state_dict keys ``model.`` / ``classification.``) and ``domains``
+    is ignored, though still iterated.  State_dict keys per mode as upstream: dense ``model.`` + ``classification_1.`` + ``classification_2.``;
+    lstm ``model_1.`` + ``model_2.`` + ``classification.``.
+
+    dense, reproduced as it is (DESIGN.md "Domain-switched heads"): with idx1 = the documents whose domain is truthy and idx2 = the rest,
+    a mixed batch runs BOTH heads over the whole batch and ``regroup`` assigns out[idx1[k]] = head_1(h)[k], out[idx2[k]] = head_2(h)[k]:
+    document i is scored from the encoder rows of document rank(i), its position inside its own group, not from its own rows.  Document r is
+    therefore read by up to two documents (idx1[r] and idx2[r]); documents r >= max(len(idx1), len(idx2)) are read by none and get a zero
+    data gradient; rows at or past the SOURCE document's length are 0, so the score there is the bias.  The loss un-pads row i by lengths[i]
+    against tags[i] as BiLSTM does.  A single-domain batch goes through classification_1 (all truthy) or classification_2 with its own rows.
+
+    lstm: a single-domain batch runs model_1 (all truthy) or model_2; a mixed batch raises the AttributeError the reference dies with
+    (:1146 hands RNN a list of lengths).
+
+    The parameters a batch does not read (the other head / encoder) keep ``grad is None`` through ``loss().backward()``, as upstream, so a
+    torch optimizer skips them; in ``grad_flat()`` their spans are zeros (``_unused_params`` names them for the autograd bridge).
+    ``domain_learning=True`` computes a domain loss upstream and discards it (:1159-1162), and no TextSegmenter option reaches it: refused."""
+
+    UPSTREAM_MIXED_LSTM = "'list' object has no attribute 'data'"      # fixture g20 lstm_mixed_msg
+    takes_domains = True             # loss_and_grad(xs, lengths, tags, domains): trainer.NativeTrainer passes batch['domain']
+
+    def __init__(self, tagset_size, embedding_dim, hidden_dim, num_layers=1, bidirectional=True, dropout_in=0.0, dropout_out=0.0,
+                 batch_first=True, LSTM=True, loss_fn='CrossEntropy', threshold=None, device=None, alpha=0.9, gamma=2, bias_adapt=False,
+                 switch_lstm_adapt=False, switch_dense_adapt=False, domain_learning=False, compute_dtype=None, seed=None):
+        super().__init__()
+        self._init_common(loss_fn, threshold, alpha, gamma, compute_dtype)
+        self._check_rnn_args(dropout_in, dropout_out, LSTM, bidirectional)
+        if domain_learning:
+            raise NotImplementedError('domain_learning=True (models/CRF.py:1119-1122, :1159-1162): the reference computes a domain loss and '
+                                      'discards it, and no TextSegmenter option reaches it; there is no behaviour to reproduce')
+        self.embedding_dim, self.hidden_dim, self.tagset_size, self.num_layers = embedding_dim, hidden_dim, tagset_size, num_layers
+        self.n_out = tagset_size if loss_fn == 'CrossEntropy' else 1
+        self.switch = 'lstm' if switch_lstm_adapt else ('dense' if switch_dense_adapt else 0)      # :1061-1110
+        self.dl = False
+        gen = torch.Generator().manual_seed(torch.initial_seed() if seed is None else seed)
+        self._hp = Hp = round_up(hidden_dim, 8)
+        groups, init, pads = [], {}, {}
+        prefixes = ('model_1.', 'model_2.') if self.switch == 'lstm' else ('model.',)
+        for pre in prefixes:
+            g, i, p = _rnn_groups(pre, embedding_dim, hidden_dim, num_layers, gen)
+            groups += g
+            init.update(i)
+            pads.update(p)
+        heads = ('classification_1', 'classification_2') if self.switch == 'dense' else ('classification',)
+        for h in heads:
+            init[h + '.weight'], init[h + '.bias'] = _linear_init(self.n_out, 2 * hidden_dim, gen)
+            if _head_pad(hidden_dim, 2):
+                pads[h + '.weight'] = _head_pad(hidden_dim, 2)
+        # one group: the two heads' weights back to back = the kernels' stacked w [2, n_out, 2Hp], then the biases = bias [2, n_out]
+        groups.append([(h + '.weight', (self.n_out, 2 * Hp)) for h in heads] + [(h + '.bias', (self.n_out,)) for h in heads])
+        self._heads = heads
+        self._init_flat(FlatLayout(groups, pads), init)
+        self._stacks = {pre: _RnnStack(self, pre, embedding_dim, hidden_dim, num_layers, tag)
+                        for pre, tag in zip(prefixes, ('r1', 'r2') if self.switch == 'lstm' else ('r',))}
+        self._unused_params = frozenset()
+
+    def _stack_names(self, pre):
+        return f'{pre}rnn.weight_ih_l0', f'{pre}rnn.bias_hh_l{self.num_layers - 1}_reverse'
+
+    def _route(self, domains):
+        """-> (encoder prefix, names of the parameters this batch does not read).  Iterates ``domains`` as separate_domains does (:1124-1130):
+        None raises TypeError."""
+        truthy = [bool(d) for d in domains]
+        any1, any2 = any(truthy), not all(truthy)
+        if self.switch == 'lstm':
+            if any1 and any2:
+                raise AttributeError(self.UPSTREAM_MIXED_LSTM)
+            pre = 'model_1.' if any1 else 'model_2.'
+            other = 'model_2.' if any1 else 'model_1.'
+            return pre, frozenset(n for n in self._layout.entries if n.startswith(other))
+        if self.switch == 'dense' and not (any1 and any2):
+            other = 'classification_2' if any1 else 'classification_1'
+            return 'model.', frozenset((other + '.weight', other + '.bias'))
+        return 'model.', frozenset()
+
+    def _head_w(self, flat):
+        return self._wspan(flat, self._heads[0] + '.weight', self._heads[-1] + '.weight', 2 * self.n_out, 2 * self._hp).view(2, self.n_out, 2 * self._hp)
+
+    def _head_b(self, flat):
+        return self._wspan(flat, self._heads[0] + '.bias', self._heads[-1] + '.bias', 2, self.n_out)
+
+    def _fwd(self, xs, lengths, domains):
+        pre, unused = self._route(domains)
+        x, Lq = self._prep_input(xs, lengths)
+        first = x[0] if isinstance(x, tuple) else x
+        B, dev = first.shape[0], first.device
+        li32 = self._prep_lengths(lengths, B, Lq, dev)
+        rnn = self._stacks[pre]
+        h, saved = rnn.forward(self._drop_in(self._to_act(x), rnn.tag), li32, B, Lq)
+        h, hmask = self._drop_out(h, rnn.tag)
+        scores = self._ws.get('scores', B * Lq, self.n_out, torch.float32, dev)
+        if self.switch == 'dense':
+            ops.switch_head_fwd(h, self._head_w(self._flat), self._head_b(self._flat), domains, B, Lq, scores)
+        else:
+            ops.head_fwd(h, self._w(self._flat, 'classification.weight'), self._w(self._flat, 'classification.bias'), scores)
+        return dict(B=B, L=Lq, li32=li32, h=h, hmask=hmask, saved=saved, rnn=rnn, unused=unused, scores=scores.view(B, Lq, self.n_out))
+
+    def loss_and_grad(self, xs, lengths, tags, domains, want_grad=True):
+        L.require_gpu()
+        st = self._fwd(xs, lengths, domains)
+        dev, B, Lq = st['scores'].device, st['B'], st['L']
+        tg = tags.to(device=dev, dtype=torch.float32).contiguous()
+        if self.loss_kind == L.LOSS_CE and tg.shape[1] != Lq:
+            raise ValueError(f'Expected input batch_size ({B * Lq}) to match target batch_size ({tg.numel()}).')     # as BiLSTM (:1224)
+        loss_out = torch.empty(2, dtype=torch.float32, device=dev)
+        dsc = self._ws.get('dscores', B * Lq, self.n_out, torch.float32, dev) if want_grad else None
+        ops.tagger_loss(self.loss_kind, st['scores'], tg, st['li32'], self.alpha, self.gamma, loss_out, dsc)
+        if want_grad:
+            self._unused_params = st['unused']
+            ops.scale_(dsc, self.loss_grad_scale)
+            g, lay = self.grad_flat(), self._layout
+            dout = self._ws.get('dout', B * Lq, 2 * self._hp, self.compute_dtype, dev)
+            if self.switch == 'dense':
+                # the head no document uses is written as exact zeros by the kernel: its span is announced like every other
+                ops.switch_head_bwd_params(st['h'], dsc, domains, B, Lq, self._head_w(g), self._head_b(g))
+                self._grads_ready(*self._span_of(self._heads[0] + '.weight', self._heads[-1] + '.bias'))
+                ops.switch_head_bwd_data(dsc, self._head_w(self._flat), domains, B, Lq, dout)
+            else:
+                ops.head_bwd_params(st['h'], dsc, lay.view(g, 'classification.weight'), lay.view(g, 'classification.bias'))
+                self._grads_ready(*self._span_of('classification.weight', 'classification.bias'))
+                ops.head_bwd_data(dsc, self._w(self._flat, 'classification.weight'), dout)
+            if self.switch == 'lstm':                      # the encoder this batch did not run: zero gradient, announced
+                other = next(p for p in self._stacks if p != st['rnn'].prefix)
+                a, b = self._span_of(*self._stack_names(other))
+                g[a:b].zero_()
+                self._grads_ready(a, b)
+            if st['hmask'] is not None:
+                ops.dropout_bwd(dout, dout, st['hmask'], self.dropout_out)
+            st['rnn'].backward(st['saved'], dout, st['li32'], B, Lq)
+        return loss_out[0], st['scores']
+
+    def loss(self, xs, lengths, tags, domains, segments=None):
+        """models/CRF.py:1141-1227."""
+        if segments is not None:
+            raise NotImplementedError('cosine auxiliary loss (models/CRF.py:23-92): no collater of the reference produces '
+                                      "batch['src_segments'] (TextSegmenter.training_step raises KeyError upstream, fixture g15)")
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self._flat_params.values()):
+            return self._autograd_loss(lambda: self.loss_and_grad(xs, lengths, tags, domains, True)[0])
+        return self.loss_and_grad(xs, lengths, tags, domains, False)[0].clone()
+
+    def forward(self, xs, lengths, domains, threshold=0.4):
+        """models/CRF.py:1229-1270."""
+        L.require_gpu()
+        with torch.no_grad():
+            st = self._fwd(xs, lengths, domains)
+            scores = st['scores'].clone()
+            tags = self._decode(scores, st['li32'], lengths, threshold)
+        return scores, tags

@@ -407,12 +407,15 @@ class _NativeLoss(torch.autograd.Function):
     def forward(ctx, model, run, *params):
         loss = run()
         ctx.model = model
+        # the parameters this step did not read (SwitchBiLSTM: the other head / encoder), as the model's loss_and_grad listed them: their
+        # gradient is None, not zeros, so .grad stays None as upstream and a torch optimizer skips them.  Models without the list: none.
+        ctx.unused = frozenset(getattr(model, '_unused_params', ()) or ())
         return loss.clone()
 
     @staticmethod
     def backward(ctx, gout):
         views = ctx.model.grad_views()
-        grads = [(v * gout).clone() for v in views.values()]
+        grads = [None if name in ctx.unused else (v * gout).clone() for name, v in views.items()]
         return (None, None, *grads)
 
 

@@ -20,7 +20,12 @@ from . import ops
 
 
 def shard_batch(batch, rank, world):
-    """Document-sharded view of a collated batch (EncoderDataset.py batch dict): rank r keeps documents r::world."""
+    """Document-sharded view of a collated batch (EncoderDataset.py batch dict): rank r keeps documents r::world (the 'domain' list too).
+
+    SwitchBiLSTM(switch='dense') is the one tagger for which a sharded batch is NOT the single-process batch: on a mixed batch the
+    reference scores document i from the encoder rows of document rank(i), its position inside its own domain group (rnn_taggers.
+    SwitchBiLSTM), and that rank is a function of the LOCAL document order -- a shard pairs documents differently than the whole batch
+    does.  Each rank computes exactly what the reference computes on its shard (what DDP does upstream); no re-pairing is attempted."""
     if world == 1:
         return batch
     out = {}
@@ -49,6 +54,13 @@ class NativeTrainer:
                  always_hook=False, exchange_schedule=None, gradient_clip_val=None, gradient_clip_algorithm='norm',
                  error_if_nonfinite=False):
         """model: a tagger from taggers.py / rnn_taggers.py (or a TextSegmenter, whose .model is used).
+
+        Three calling conventions of ``loss_and_grad``: (x, lengths, tags); (x, x2, lengths, tags) for a late-fusion model on a batch with
+        'src_tokens2'; (x, lengths, tags, batch['domain']) for a model that takes domains (``takes_domains``: SwitchBiLSTM).  The
+        parameters such a model does not read in a step (the other head / encoder) have a ZERO gradient here: the flat optimizer steps
+        the whole buffer, so Adam leaves them where they are while their moments are zero (a first step on a single-domain batch) and
+        afterwards goes on decaying the moments and moving them, and SGD applies weight decay and momentum -- whereas torch.optim on the
+        autograd front end sees grad None and skips them altogether, as upstream.
 
         token_weighted: the reference's loss is a mean over the LOCAL batch's valid sentences (models/CRF.py:352), so plain data
         parallelism (DDP included) averages shard means; with ragged shards that is not the global mean.  True weights each
@@ -237,6 +249,8 @@ class NativeTrainer:
         m._grad_hook = self._on_grads_ready if overlapped else None
         if batch.get('src_tokens2') is not None and hasattr(m, '_rnn2'):
             loss, _ = m.loss_and_grad(x, batch['src_tokens2'], lengths, tags, True)
+        elif getattr(m, 'takes_domains', False):
+            loss, _ = m.loss_and_grad(x, lengths, tags, batch['domain'], True)
         else:
             loss, _ = m.loss_and_grad(x, lengths, tags, True)
         if overlapped:
