@@ -375,6 +375,36 @@ int mts_pair_score_bwd(void* stream, int dtype, int B, int L, int H, const void*
                        const float* dscores, void* dF, int lddf, void* dG, int lddg);
 
 /* ---------------------------------------------------------------------------------------------
+ * Cosine auxiliary segment loss.  Replaces cosine_loss / aggregate_embeddings + nn.CosineEmbeddingLoss() of the `segments=` branch of
+ * BiLSTM.loss and BiLSTMLateFusion.loss (models/CRF.py:23-92, :322-337, :427-442).
+ * x, dx: [B*L, W] act dtype with leading dimensions in ELEMENTS (late fusion hands in a view).  int32 device tables, built on the host
+ * from the batch's segment lists:
+ *   seg_table  [n_seg, 8]:  {document, begin row, end row, tail flag, positive pair, negative pair with this segment as FIRST member,
+ *                           negative pair with it as SECOND member, 0}; rows are relative to the document, pair entries are -1 for "none".
+ *                           A document's listed segments and its tail (end of the last listed segment .. length; may be empty) are adjacent.
+ *   pair_table [n_pair, 4]: {segment a, segment b, target +1 | -1, 0}.  target +1: (even rows of a, odd rows of a), a == b;
+ *                           target -1: (all rows of a, all rows of b).
+ *   row_map    [B*L]:       2 * segment + parity of the row inside its segment, or -1 for a row in no segment.
+ * forward:  cos_p = a.b / sqrt((|a|^2 + 1e-12)(|b|^2 + 1e-12)) from fp32 row sums; term_p = 1 - cos_p (target +1) | max(cos_p, 0) (target -1);
+ *           loss_out fp32 [2] = {mean of the terms, n_pair}; pair_cos (fp32 [n_pair], may be NULL) receives every cos_p.  x is read once.
+ *           n_pair == 0 writes {0, 0} and launches nothing.
+ * backward: dx[r, :] (+)= scale * d(sum of the terms)/dx[r, :]  (the caller folds 1 / n_pair into scale; the clamp passes the gradient
+ *           where cos >= 0).  accumulate = 1 adds into dx and leaves rows in no segment alone, accumulate = 0 overwrites every row, rows in no
+ *           segment with zeros.  Needs the workspace of the forward call untouched.  Gather form, no atomics: bitwise reproducible.
+ * workspace: mts_segment_cosine_workspace(n_seg, n_pair, W) bytes, 16-byte aligned: fp32 row sums and gradient vectors per segment
+ *           and parity, four statistics per pair.
+ * A table entry outside its range contributes nothing and no address is formed from it.
+ * Covered: W a multiple of 8 (bf16) / 4 (fp32); x, dx, their leading dimensions and the workspace 16-byte aligned; anything else is
+ * MTS_ERR_UNSUPPORTED before any launch.
+ * ------------------------------------------------------------------------------------------- */
+size_t mts_segment_cosine_workspace(int n_seg, int n_pair, int W);
+int mts_segment_cosine_fwd(void* stream, int dtype, int B, int L, int W, const void* x, int ldx, int n_seg, const int32_t* seg_table,
+                           int n_pair, const int32_t* pair_table, float* loss_out, float* pair_cos, void* workspace);
+int mts_segment_cosine_bwd(void* stream, int dtype, int B, int L, int W, int n_seg, const int32_t* seg_table, int n_pair,
+                           const int32_t* pair_table, const int32_t* row_map, float scale, int accumulate, void* dx, int lddx,
+                           void* workspace);
+
+/* ---------------------------------------------------------------------------------------------
  * Tagger head tail: loss + its gradient, and greedy decode.
  * Replaces: the un-pad loop + BCE/Focal/CE of models/CRF.py:342-356 (=:447-461, :581-595),
  * models/focal_loss.py:38-57, and decode models/CRF.py:362-369.

@@ -90,6 +90,9 @@ SIGNATURES = {
     'mts_rmsnorm_bwd': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'mts_pair_score_fwd': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
     'mts_pair_score_bwd': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i]),
+    'mts_segment_cosine_workspace': (_sz, [_i, _i, _i]),
+    'mts_segment_cosine_fwd': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    'mts_segment_cosine_bwd': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _f, _i, _vp, _i, _vp]),
     'mts_tagger_loss_workspace': (_sz, [_i, _i]),
     'mts_tagger_loss': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _sz, _vp, _i]),
     'mts_greedy_decode': (_i, [_vp, _i, _i, _i, _vp, _vp, _f, _vp]),

@@ -2,7 +2,7 @@
 (EncoderDataset.py:18-152, :154-232): ragged per-document embeddings -> zero-padded batch dict
 
     {'id', 'src_tokens' [B, Lmax, D] fp32, 'src_lengths' [B] int64, 'tgt_tokens' [B, Lmax] fp32 (pad -1, or 0 for CRF),
-     'src_tokens2' or None, 'domain' or None}
+     'src_tokens2' or None, 'domain' or None}   (+ 'src_segments' with ``segments=True``, an extension: see AudioPortionDataset.__init__)
 
 with ``truncate=True`` meaning "pad/truncate to exactly truncate_value" (3600 for the Transformer, train_fit.py:104-106).
 Host-side only; the PCA/UMAP projection of the reference (:49-69, buggy re-slicing) is out of scope.
@@ -133,9 +133,14 @@ def _merge_native(values, truncate, tv, ring, slot, field, dtype, threads, pad=0
 class AudioPortionDataset(Dataset):
     def __init__(self, lines, tag_to_ix, encoder='x-vectors', CRF=True, truncate=True, truncate_value=100, umap_project=False,
                  umap_project_value=100, umap_class=None, second_input=None, domain_adapt=False, pin_memory=False, wire_dtype='fp32',
-                 pin_slots=4, collate_threads=8):
+                 pin_slots=4, collate_threads=8, segments=False):
         if umap_project:
             raise NotImplementedError('PCA/UMAP projection (EncoderDataset.py:49-69) is outside the hot path')
+        # segments (extension, default False: the batch dict keeps the reference's keys): True adds 'src_segments', what TextSegmenter(
+        # cosine_loss=True) reads and no collater of the reference makes -- per document the boundary positions [t + 1 for t < length if
+        # target[t] == 1], so every listed segment ends with its boundary sentence and the rest of the document is the last negative
+        # pair's partner; a document without a boundary gets []
+        self.segments = bool(segments)
         if wire_dtype not in ('fp32', 'bf16'):
             raise ValueError("wire_dtype must be 'fp32' or 'bf16'")
         self.minus = 0 if CRF else 1                                   # EncoderDataset.py:23
@@ -217,8 +222,18 @@ class AudioPortionDataset(Dataset):
         tgt = _pad_native(ptrs[ii], rows[ii], 0, torch.float32, self.truncate, self.tv, ring, slot, 'tgt_tokens', torch.float32, 1, pad=-float(self.minus))
         n = tab['e'][2][ii]
         lengths = torch.from_numpy(np.minimum(n, self.tv) if self.truncate else n.copy())
-        return {'id': torch.from_numpy(ii.copy()), 'src_tokens': out['src_tokens'], 'src_lengths': lengths, 'tgt_tokens': tgt,
-                'src_tokens2': out['src_tokens2'], 'domain': [self.domain[i] for i in idx] if self.da else None}
+        batch = {'id': torch.from_numpy(ii.copy()), 'src_tokens': out['src_tokens'], 'src_lengths': lengths, 'tgt_tokens': tgt,
+                 'src_tokens2': out['src_tokens2'], 'domain': [self.domain[i] for i in idx] if self.da else None}
+        if self.segments:
+            batch['src_segments'] = self._segments_of(tgt, lengths)
+        return batch
+
+    @staticmethod
+    def _segments_of(tgt_tokens, src_lengths):
+        """'src_segments' of a collated batch: per document the positions just behind its boundary sentences, [t + 1 for t < length if
+        tgt[t] == 1] (strictly ascending, 0 < s <= length: what ops.segment_table accepts)"""
+        tg = tgt_tokens.numpy() if tgt_tokens.dtype == torch.float32 else tgt_tokens.to(torch.float32).numpy()
+        return [(np.flatnonzero(tg[b, :int(n)] == 1) + 1).tolist() for b, n in enumerate(src_lengths.tolist())]
 
     def __len__(self):
         return len(self.embeddings)
@@ -256,9 +271,12 @@ class AudioPortionDataset(Dataset):
             src_lengths = torch.LongTensor([min(self.tv, len(s['embeddings'])) for s in samples])
         else:
             src_lengths = torch.LongTensor([len(s['embeddings']) for s in samples])
-        return {'id': torch.tensor([int(s['id']) for s in samples]), 'src_tokens': src_tokens, 'src_lengths': src_lengths,
-                'tgt_tokens': tgt_tokens, 'src_tokens2': src_tokens2,
-                'domain': [s['domain'] for s in samples] if self.da else None}
+        batch = {'id': torch.tensor([int(s['id']) for s in samples]), 'src_tokens': src_tokens, 'src_lengths': src_lengths,
+                 'tgt_tokens': tgt_tokens, 'src_tokens2': src_tokens2,
+                 'domain': [s['domain'] for s in samples] if self.da else None}
+        if self.segments:
+            batch['src_segments'] = self._segments_of(tgt_tokens, src_lengths)
+        return batch
 
 
 class AudioPortionDatasetInference(Dataset):

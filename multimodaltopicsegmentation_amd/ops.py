@@ -387,6 +387,122 @@ def pair_score_bwd(F, G, dscores, B, Lq, dF, dG):
                                      ptr(dF), dF.stride(0), ptr(dG), dG.stride(0)))
 
 
+class SegmentTable:
+    """Host tables of the cosine auxiliary segment loss (include/mts.h "Cosine auxiliary segment loss"), int32 numpy arrays:
+    seg [n_seg, 8], pair [n_pair, 4], row_map [B * L]."""
+
+    def __init__(self, seg, pair, row_map, B, L):
+        self.seg, self.pair, self.row_map, self.B, self.L = seg, pair, row_map, B, L
+        self.n_seg, self.n_pair = int(seg.shape[0]), int(pair.shape[0])
+
+
+def segment_table(segments, lengths, B, L):
+    """Host side of the cosine auxiliary loss: ``segments[b]`` = the segment ends of document b (models/CRF.py:23-69) -> SegmentTable.
+
+    Per document with ends s_0 < s_1 < ..: the listed segments [0, s_0), [s_0, s_1), .. and the tail [s_last, lengths[b]) (maybe empty);
+    a positive pair for every listed segment of more than one row, a negative pair (segment, next segment) for every listed segment.
+    Pairs are numbered as upstream concatenates them: every positive pair in document order, then every negative pair.  A document with
+    an empty list has no segment and no pair.  Entries of ``segments`` past B are ignored; fewer than B raise IndexError, as upstream.
+    Every list must be strictly ascending with 0 < s <= lengths[b] (clamped to L): anything else is a ValueError -- upstream, Python
+    slicing silently yields empty or clipped slices there (DESIGN.md "Cosine auxiliary segment loss")."""
+    import numpy as np
+    B, L = int(B), int(L)
+    if isinstance(segments, torch.Tensor):
+        segments = segments.tolist()
+    if isinstance(segments, (str, bytes)) or not hasattr(segments, '__len__') or not hasattr(segments, '__getitem__'):
+        raise ValueError(f'segments must be a sequence of lists of segment ends, one per document; got {type(segments).__name__}')
+    if lengths is None:
+        lens = [L] * B
+    else:
+        lens = [int(v) for v in (lengths.tolist() if hasattr(lengths, 'tolist') else lengths)]
+        if len(lens) != B:
+            raise ValueError(f'lengths has {len(lens)} entries for a batch of {B} documents')
+    if len(segments) < B:
+        raise IndexError('list index out of range')                   # segment_indeces[batch_index], models/CRF.py:34
+    n = np.clip(np.asarray(lens, dtype=np.int64), 0, L)
+    docs = []
+    for b in range(B):
+        d = segments[b]
+        arr = np.asarray(d.tolist() if hasattr(d, 'tolist') else d)
+        if arr.size and (arr.ndim != 1 or arr.dtype.kind not in 'iu' or any(isinstance(v, bool) for v in d)):
+            raise ValueError(f'segments[{b}] must be a flat list of integers; got {list(d)!r}')
+        docs.append(arr.astype(np.int64).reshape(-1))
+    counts = np.array([a.size for a in docs], dtype=np.int64)
+    K = int(counts.sum())
+    ends = np.concatenate(docs) if K else np.zeros(0, dtype=np.int64)
+    doc = np.repeat(np.arange(B, dtype=np.int64), counts)
+    first = np.zeros(K, dtype=bool)
+    first[(np.cumsum(counts) - counts)[counts > 0]] = True            # the first listed end of its document
+    begins = np.where(first, 0, np.concatenate(([0], ends[:-1]))) if K else ends
+    bad = ~((begins < ends) & (ends <= n[doc]))
+    if bad.any():
+        b = int(doc[np.flatnonzero(bad)[0]])
+        raise ValueError(f'segments[{b}] = {docs[b].tolist()} must be strictly ascending with 0 < s <= {int(n[b])} (the length of document {b})')
+    # segment order: a document's listed segments, then its tail (last end .. length: the last negative pair's partner, maybe empty)
+    has = counts > 0
+    rank = np.cumsum(has) - has                                       # documents with a list in front of document b
+    S = K + int(has.sum())
+    seg = np.zeros((S, 8), dtype=np.int32)
+    seg[:, 4:7] = -1
+    at = np.arange(K, dtype=np.int64) + rank[doc]                     # where listed segment i goes
+    seg[at, 0], seg[at, 1], seg[at, 2] = doc, begins, ends
+    hd = np.flatnonzero(has)
+    tail = np.cumsum(counts)[hd] + rank[hd]
+    seg[tail, 0], seg[tail, 1], seg[tail, 2], seg[tail, 3] = hd, ends[np.cumsum(counts)[hd] - 1] if K else 0, n[hd], 1
+    # pairs as upstream concatenates them: every positive pair (listed segments of more than one row), then every negative pair
+    pos = at[(ends - begins) > 1]
+    npos = pos.size
+    pair = np.zeros((npos + K, 4), dtype=np.int32)
+    pair[:npos, 0], pair[:npos, 1], pair[:npos, 2] = pos, pos, 1
+    pair[npos:, 0], pair[npos:, 1], pair[npos:, 2] = at, at + 1, -1
+    seg[pos, 4] = np.arange(npos)
+    seg[at, 5] = seg[at + 1, 6] = npos + np.arange(K)
+    # row map in one vector pass: row doc * L + begin + k of segment s -> 2 s + (k & 1)
+    row_map = np.full(B * L, -1, dtype=np.int32)
+    n_rows = (seg[:, 2] - seg[:, 1]).astype(np.int64)
+    if n_rows.sum():
+        sid = np.repeat(np.arange(S, dtype=np.int64), n_rows)
+        k = np.arange(int(n_rows.sum()), dtype=np.int64) - np.repeat(np.cumsum(n_rows) - n_rows, n_rows)
+        row_map[np.repeat(seg[:, 0].astype(np.int64) * L + seg[:, 1], n_rows) + k] = (2 * sid + (k & 1)).astype(np.int32)
+    return SegmentTable(seg, pair, row_map, B, L)
+
+
+class _DeviceSegmentTable:
+    def __init__(self, tab, device):
+        import numpy as np
+        self.n_seg, self.n_pair, self.B, self.L = tab.n_seg, tab.n_pair, tab.B, tab.L
+        flat = torch.from_numpy(np.concatenate([tab.seg.ravel(), tab.pair.ravel(), tab.row_map])).to(device)      # one upload
+        a, b = tab.seg.size, tab.seg.size + tab.pair.size
+        self.seg, self.pair, self.row_map = flat[:a], flat[a:b], flat[b:]
+
+
+def segment_tables(segments, lengths, B, L, device):
+    """segment_table on the device: validated and built on the host for every call (vector passes: well under a millisecond at
+    64 x 256), then one small upload."""
+    return _DeviceSegmentTable(segment_table(segments, lengths, B, L), device)
+
+
+def segment_cosine_fwd(x, tab, loss_out, pair_cos=None):
+    """loss_out fp32 [2] = {mean cosine-embedding term over tab's pairs, n_pair} (include/mts.h).  x: [B*L, W] view in the activation
+    dtype (row stride free); tab: segment_tables(...).  -> the workspace, which segment_cosine_bwd needs untouched."""
+    W = x.shape[1]
+    assert x.shape[0] == tab.B * tab.L and x.stride(1) == 1
+    ws = _scratch(lib.mts_segment_cosine_workspace(tab.n_seg, tab.n_pair, W), x.device, 'segcos')
+    with _timed(('segcos_fwd', tab.B, tab.L, W)):
+        check(lib.mts_segment_cosine_fwd(stream_ptr(), dtype_code(x.dtype), tab.B, tab.L, W, ptr(x), x.stride(0), tab.n_seg, ptr(tab.seg),
+                                         tab.n_pair, ptr(tab.pair), ptr(loss_out), ptr(pair_cos), ptr(ws)))
+    return ws
+
+
+def segment_cosine_bwd(tab, scale, dx, ws, accumulate=True):
+    """dx[r] (+)= scale * d(sum of the pair terms)/dx[r]; rows in no segment: untouched (accumulate) or written 0."""
+    W = dx.shape[1]
+    assert dx.shape[0] == tab.B * tab.L and dx.stride(1) == 1
+    with _timed(('segcos_bwd', tab.B, tab.L, W)):
+        check(lib.mts_segment_cosine_bwd(stream_ptr(), dtype_code(dx.dtype), tab.B, tab.L, W, tab.n_seg, ptr(tab.seg), tab.n_pair, ptr(tab.pair),
+                                         ptr(tab.row_map), float(scale), int(accumulate), ptr(dx), dx.stride(0), ptr(ws)))
+
+
 def tagger_loss(kind, scores, targets, lengths, alpha, gamma, loss_out, dscores, row_src=None, batch_shape=None):
     """scores [B, L, n_out]; or, for a packed batch, [n_rows, n_out] with row_src (int32 [n_rows]) and batch_shape = (B, L)."""
     if row_src is None:

@@ -15,7 +15,7 @@ drop-in user who hands the tagger host batches would get half the resident-input
   * ``wire_dtype='bf16'`` converts ``src_tokens`` / ``src_tokens2`` to bf16 on the HOST while staging (half the PCIe bytes; the
     recurrent taggers round their input to bf16 first thing anyway, so for them the result is bit-identical to fp32 transport --
     tests/test_gpu_prefetch.py; the transformer reads fp32 embeddings into an fp32 LayerNorm, so there it is an approximation and
-    stays opt-in).  ``src_lengths``, ``id`` and ``domain`` stay on the host, where the taggers read them.
+    stays opt-in).  ``src_lengths``, ``id``, ``domain`` and ``src_segments`` stay on the host, where the taggers read them.
 
 Nothing here touches the arithmetic of the path; bench.py --h2d reports the step time with this loader in the loop as a separate
 line, never mixed into ``value`` (which is quoted with inputs resident in HBM).

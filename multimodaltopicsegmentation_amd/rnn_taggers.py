@@ -271,6 +271,46 @@ class _RnnTaggerBase(_TaggerBase):
         ops.dropout_fwd(h, out, self.dropout_out, self._drop_seed(), mask=mask)
         return out, mask
 
+    COSINE_WEIGHT = 0.1              # tot_loss = 0.1 * cos_loss + loss (models/CRF.py:335, :440)
+
+    def _segment_tables(self, segments, xs, lengths, tags):
+        """Host tables of the cosine auxiliary loss for this batch, validated before anything is launched (ops.segment_table), and the
+        target-shape check of the reference's unmasked main loss (models/CRF.py:331-333): all three loss functions refuse targets that do
+        not cover exactly max(lengths) positions."""
+        x1, _, B, Lin, _ = self._split_input(xs)
+        Lq = min(int(lengths.max()) if lengths is not None else Lin, Lin)
+        tab = ops.segment_tables(segments, lengths, B, Lq, x1.device)
+        if tags.shape[1] != Lq:
+            n_in, n_tg = B * Lq, tags.numel()
+            if self.loss_kind == L.LOSS_CE:
+                raise ValueError(f'Expected input batch_size ({n_in}) to match target batch_size ({n_tg}).')
+            if self.loss_kind == L.LOSS_FOCAL:
+                raise ValueError(f'Target size (torch.Size([{n_tg}])) must be the same as input size (torch.Size([{n_in}]))')
+            raise ValueError(f'Using a target size (torch.Size([{n_tg}])) that is different to the input size (torch.Size([{n_in}])) is '
+                             'deprecated. Please ensure they have the same size.')
+        if self.loss_kind == L.LOSS_BCE and tags.numel():
+            # nn.BCELoss over ALL positions: the collater's pad -1 is refused upstream (fixture g21 err_bce_pad); pad 0 (the CRF collater's)
+            # runs.  Targets still on the host (the collater's) are checked there; device targets cost one synchronisation per step
+            lo, hi = tags.min(), tags.max()
+            if float(lo) < 0.0 or float(hi) > 1.0:
+                raise RuntimeError('all elements of target should be between 0 and 1')
+        return tab
+
+    def _cosine_fwd(self, tab, act, loss_out):
+        """loss_out[0] += 0.1 * (mean cosine-embedding term over the batch's pairs) -> the kernels' workspace (None without a pair: the
+        reference's cosine term is then the int 0)."""
+        if tab.n_pair == 0:
+            return None
+        cos_out = self._ws.get('cos_out', 1, 2, torch.float32, act.device).view(-1)
+        ws = ops.segment_cosine_fwd(act, tab, cos_out)
+        loss_out[:1].add_(cos_out[:1], alpha=self.COSINE_WEIGHT)
+        return ws
+
+    def _cosine_bwd(self, tab, ws, dact):
+        """the cosine term's gradient, added into the head's data gradient"""
+        if ws is not None:
+            ops.segment_cosine_bwd(tab, self.COSINE_WEIGHT * self.loss_grad_scale / tab.n_pair, dact, ws, accumulate=True)
+
     def _to_act(self, x):
         if isinstance(x, tuple):                                       # K-split pair: concat + cast in one pass over the two fp32 parts
             a, b = (t.reshape(-1, t.shape[-1]).to(torch.float32).contiguous() for t in x)
@@ -294,6 +334,7 @@ class _RnnTaggerBase(_TaggerBase):
 
 class BiLSTM(_RnnTaggerBase):
     """models/CRF.py:274-369."""
+    takes_segments = True            # loss_and_grad(..., segments=): trainer.NativeTrainer(cosine_loss=True) passes batch['src_segments']
 
     def __init__(self, tagset_size, embedding_dim, hidden_dim, num_layers=1, bidirectional=True, dropout_in=0.0, dropout_out=0.0,
                  batch_first=True, LSTM=True, loss_fn='CrossEntropy', threshold=None, device=None, alpha=0.9, gamma=2,
@@ -325,8 +366,12 @@ class BiLSTM(_RnnTaggerBase):
         ops.head_fwd(h, self._w(self._flat, 'classification.weight'), self._w(self._flat, 'classification.bias'), scores)
         return dict(B=B, L=Lq, li32=li32, h=h, hmask=hmask, saved=saved, scores=scores.view(B, Lq, self.n_out))
 
-    def loss_and_grad(self, xs, lengths, tags, want_grad=True):
+    def loss_and_grad(self, xs, lengths, tags, want_grad=True, segments=None):
+        """segments (one list of segment ends per document, the batch's 'src_segments'): the `segments=` branch of the reference (models/CRF.py:
+        322-337) -- 0.1 x the cosine auxiliary loss over the encoder output is added, and the main loss runs over ALL B x max(len)
+        positions, padded ones included (DESIGN.md "Cosine auxiliary segment loss")."""
         L.require_gpu()
+        tab = self._segment_tables(segments, xs, lengths, tags) if segments is not None else None
         st = self._fwd(xs, lengths)
         dev, B, Lq = st['scores'].device, st['B'], st['L']
         tg = tags.to(device=dev, dtype=torch.float32).contiguous()
@@ -335,7 +380,9 @@ class BiLSTM(_RnnTaggerBase):
             raise ValueError(f'Expected input batch_size ({B * Lq}) to match target batch_size ({tg.numel()}).')
         loss_out = torch.empty(2, dtype=torch.float32, device=dev)
         dsc = self._ws.get('dscores', B * Lq, self.n_out, torch.float32, dev) if want_grad else None
-        ops.tagger_loss(self.loss_kind, st['scores'], tg, st['li32'], self.alpha, self.gamma, loss_out, dsc)
+        # with segments the reference does not un-pad (CRF.py:331): every document counts max(len) rows (lengths = NULL)
+        ops.tagger_loss(self.loss_kind, st['scores'], tg, st['li32'] if tab is None else None, self.alpha, self.gamma, loss_out, dsc)
+        cos_ws = self._cosine_fwd(tab, st['h'], loss_out) if tab is not None else None
         if want_grad:
             ops.scale_(dsc, self.loss_grad_scale)
             g, lay = self.grad_flat(), self._layout
@@ -343,19 +390,17 @@ class BiLSTM(_RnnTaggerBase):
             self._grads_ready(*self._span_of('classification.weight', 'classification.bias'))
             dout = self._ws.get('dout', B * Lq, 2 * self._hp, self.compute_dtype, dev)
             ops.head_bwd_data(dsc, self._w(self._flat, 'classification.weight'), dout)
+            self._cosine_bwd(tab, cos_ws, dout)
             if st['hmask'] is not None:
                 ops.dropout_bwd(dout, dout, st['hmask'], self.dropout_out)
             self._rnn.backward(st['saved'], dout, st['li32'], B, Lq)
         return loss_out[0], st['scores']
 
     def loss(self, xs, lengths, tags, segments=None):
-        """models/CRF.py:319-356 (segments / cosine auxiliary loss: SURVEY.md §8f 'next')."""
-        if segments is not None:
-            raise NotImplementedError('cosine auxiliary loss (models/CRF.py:23-92): no collater of the reference produces '
-                                      "batch['src_segments'] (TextSegmenter.training_step raises KeyError upstream, fixture g15)")
+        """models/CRF.py:319-356."""
         if torch.is_grad_enabled() and any(p.requires_grad for p in self._flat_params.values()):
-            return self._autograd_loss(lambda: self.loss_and_grad(xs, lengths, tags, True)[0])
-        return self.loss_and_grad(xs, lengths, tags, False)[0].clone()
+            return self._autograd_loss(lambda: self.loss_and_grad(xs, lengths, tags, True, segments)[0])
+        return self.loss_and_grad(xs, lengths, tags, False, segments)[0].clone()
 
     def forward(self, xs, lenghts, threshold=0.4):
         """models/CRF.py:358-369."""
@@ -369,6 +414,7 @@ class BiLSTM(_RnnTaggerBase):
 
 class BiLSTMLateFusion(_RnnTaggerBase):
     """models/CRF.py:371-479: two independent RNNs, plain concat (there is no gate in the reference), one head."""
+    takes_segments = True            # as BiLSTM
     concurrent_encoders = True       # model1 / model2 on two HIP streams (bitwise the same results).  Under a data-parallel hook too:
                                      # model2's spans are announced from inside `with stream(side)`, so the collective is issued
                                      # with the side stream current and waits on exactly the kernels that wrote the span (RCCL and
@@ -427,14 +473,17 @@ class BiLSTMLateFusion(_RnnTaggerBase):
         ops.head_fwd(cat, self._w(self._flat, 'classification.weight'), self._w(self._flat, 'classification.bias'), scores)
         return dict(B=B, L=Lq, li32=li32, cat=cat, s1=s1, s2=s2, m1=m1, m2=m2, scores=scores.view(B, Lq, self.n_out))
 
-    def loss_and_grad(self, x1, x2, lengths, tags, want_grad=True):
+    def loss_and_grad(self, x1, x2, lengths, tags, want_grad=True, segments=None):
+        """segments: as BiLSTM.loss_and_grad (models/CRF.py:427-442); the cosine loss reads the concatenation of the two encoders' outputs."""
         L.require_gpu()
+        tab = self._segment_tables(segments, x1, lengths, tags) if segments is not None else None
         st = self._fwd(x1, x2, lengths)
         dev, B, Lq, H = x1.device, st['B'], st['L'], self._hp
         tg = tags.to(device=dev, dtype=torch.float32).contiguous()
         loss_out = torch.empty(2, dtype=torch.float32, device=dev)
         dsc = self._ws.get('dscores', B * Lq, self.n_out, torch.float32, dev) if want_grad else None
-        ops.tagger_loss(self.loss_kind, st['scores'], tg, st['li32'], self.alpha, self.gamma, loss_out, dsc)
+        ops.tagger_loss(self.loss_kind, st['scores'], tg, st['li32'] if tab is None else None, self.alpha, self.gamma, loss_out, dsc)
+        cos_ws = self._cosine_fwd(tab, st['cat'], loss_out) if tab is not None else None
         if want_grad:
             ops.scale_(dsc, self.loss_grad_scale)
             g, lay = self.grad_flat(), self._layout
@@ -442,6 +491,7 @@ class BiLSTMLateFusion(_RnnTaggerBase):
             self._grads_ready(*self._span_of('classification.weight', 'classification.bias'))
             dcat = self._ws.get('dcat', B * Lq, 4 * H, self.compute_dtype, dev)
             ops.head_bwd_data(dsc, self._w(self._flat, 'classification.weight'), dcat)
+            self._cosine_bwd(tab, cos_ws, dcat)
             d1 = self._ws.get('dout1', B * Lq, 2 * H, self.compute_dtype, dev)
             d2 = self._ws.get('dout2', B * Lq, 2 * H, self.compute_dtype, dev)
             d1.copy_(dcat[:, :2 * H])
@@ -465,12 +515,9 @@ class BiLSTMLateFusion(_RnnTaggerBase):
 
     def loss(self, x1, x2, lengths, tags, segments=None):
         """models/CRF.py:420-461."""
-        if segments is not None:
-            raise NotImplementedError('cosine auxiliary loss (models/CRF.py:23-92): no collater of the reference produces '
-                                      "batch['src_segments'] (TextSegmenter.training_step raises KeyError upstream, fixture g15)")
         if torch.is_grad_enabled() and any(p.requires_grad for p in self._flat_params.values()):
-            return self._autograd_loss(lambda: self.loss_and_grad(x1, x2, lengths, tags, True)[0])
-        return self.loss_and_grad(x1, x2, lengths, tags, False)[0].clone()
+            return self._autograd_loss(lambda: self.loss_and_grad(x1, x2, lengths, tags, True, segments)[0])
+        return self.loss_and_grad(x1, x2, lengths, tags, False, segments)[0].clone()
 
     def forward(self, x1, x2, lenghts, threshold=0.4):
         """models/CRF.py:463-479."""

@@ -20,7 +20,8 @@ from . import ops
 
 
 def shard_batch(batch, rank, world):
-    """Document-sharded view of a collated batch (EncoderDataset.py batch dict): rank r keeps documents r::world (the 'domain' list too).
+    """Document-sharded view of a collated batch (EncoderDataset.py batch dict): rank r keeps documents r::world (the 'domain' and
+    'src_segments' lists too: a document's segment ends travel with it).
 
     SwitchBiLSTM(switch='dense') is the one tagger for which a sharded batch is NOT the single-process batch: on a mixed batch the
     reference scores document i from the encoder rows of document rank(i), its position inside its own domain group (rnn_taggers.
@@ -52,7 +53,7 @@ def local_loss_count(model, batch):
 class NativeTrainer:
     def __init__(self, model, lr=1e-3, optimizer='Adam', process_group=None, token_weighted=False, grad_exchange_dtype='fp32',
                  always_hook=False, exchange_schedule=None, gradient_clip_val=None, gradient_clip_algorithm='norm',
-                 error_if_nonfinite=False):
+                 error_if_nonfinite=False, cosine_loss=False):
         """model: a tagger from taggers.py / rnn_taggers.py (or a TextSegmenter, whose .model is used).
 
         Three calling conventions of ``loss_and_grad``: (x, lengths, tags); (x, x2, lengths, tags) for a late-fusion model on a batch with
@@ -91,6 +92,11 @@ class NativeTrainer:
         coefficient applied) are 0-d fp32 device tensors valid on the step's stream until the next step overwrites them; they
         stay None when clipping is off or by value.  model.grad_flat() itself is left unscaled and unclipped.
 
+        cosine_loss: True passes segments=batch['src_segments'] (one list of segment ends per document; AudioPortionDataset(...,
+        segments=True) makes them) to BiLSTM / BiLSTMLateFusion.loss_and_grad: the reference's 0.1 x cosine auxiliary loss (TextSegmenter(
+        cosine_loss=True), models/CRF.py:23-92).  A batch without the key raises KeyError, as upstream.  Not with token_weighted=True: the
+        cosine term is a mean over the rank's PAIRS, a count of its own that the sentence weighting does not describe (ValueError).
+
         error_if_nonfinite ('norm' only, as clip_grad_norm_): True reads the norm on the host (the one mode that synchronises) and
         raises RuntimeError before the optimizer launch when it is NaN or Inf, leaving parameters, moments and step_count as they
         were; False lets it propagate as torch does (coefficient NaN, parameters NaN)."""
@@ -103,6 +109,13 @@ class NativeTrainer:
         self._m = self._v = None
         self._comm_stream = None
         self.token_weighted = bool(token_weighted)
+        self.cosine_loss = bool(cosine_loss)
+        if self.cosine_loss and not getattr(self.model, 'takes_segments', False):
+            raise NotImplementedError(f'cosine_loss=True: {type(self.model).__name__}.loss_and_grad takes no segments (the cosine auxiliary '
+                                      'loss is built for BiLSTM and BiLSTMLateFusion)')
+        if self.cosine_loss and self.token_weighted:
+            raise ValueError('cosine_loss=True cannot be combined with token_weighted=True: the cosine auxiliary loss averages over the '
+                             "rank's segment pairs, which the per-sentence weighting does not cover")
         self.always_hook = bool(always_hook) and dist.is_available() and dist.is_initialized()
         if grad_exchange_dtype not in ('fp32', 'bf16'):
             raise ValueError("grad_exchange_dtype must be 'fp32' or 'bf16'")
@@ -247,7 +260,13 @@ class NativeTrainer:
         self._pending = []
         self._inflight_shards = []
         m._grad_hook = self._on_grads_ready if overlapped else None
-        if batch.get('src_tokens2') is not None and hasattr(m, '_rnn2'):
+        if self.cosine_loss:
+            segments = batch['src_segments']              # KeyError without it, as TextSegmenter.training_step
+            if batch.get('src_tokens2') is not None and hasattr(m, '_rnn2'):
+                loss, _ = m.loss_and_grad(x, batch['src_tokens2'], lengths, tags, True, segments=segments)
+            else:
+                loss, _ = m.loss_and_grad(x, lengths, tags, True, segments=segments)
+        elif batch.get('src_tokens2') is not None and hasattr(m, '_rnn2'):
             loss, _ = m.loss_and_grad(x, batch['src_tokens2'], lengths, tags, True)
         elif getattr(m, 'takes_domains', False):
             loss, _ = m.loss_and_grad(x, lengths, tags, batch['domain'], True)
