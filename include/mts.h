@@ -421,6 +421,22 @@ int mts_tagger_loss(void* stream, int loss_kind, int B, int L, int Lt, int n_out
 /* tags_out: uint8 [B, L]; positions >= length are 0.  prob > threshold, strict; prob = sigmoid (n_out 1) or softmax[..., 1] (n_out 2..4). */
 int mts_greedy_decode(void* stream, int B, int L, int n_out, const float* scores, const int32_t* lengths,
                       float threshold, uint8_t* tags_out);
+/* DECISION-THRESHOLD SWEEP.  Replaces the host loop of models/lightning_model.py:435-553 (the disabled validation-epoch hook) over
+ * compute_Pk / compute_window_diff / f1_score: for every document b and threshold j the six integers from which Pk, WindowDiff and
+ * boundary-F1 follow exactly.  scores fp32 [B, L, n_out], n_out 1..4; targets fp32 [B, Lt], Lt >= L, 0 / 1 inside a document's length
+ * (pad values are never read); lengths int32 [B], NULL = every document has L sentences (clamped to 0..L); thresholds DEVICE fp32 [T],
+ * 1 <= T <= 64, any order; counts_out int32 [B, T, 6] = {pk_err, wd_err, windows, tp, fp, fn}.  For a document of n sentences:
+ *   h_i = p_i > thresholds[j], strict, p_i the probability of mts_greedy_decode, same bits;  t_i = (targets[b, i] == 1)
+ *   pos_x(i) = sum_{m < i} x_m  (the segment index of sentence i once the last sentence is forced to a boundary, as compute_Pk does)
+ *   nseg = 1 + sum_{i < n-1} t_i;  k = max(round_half_even(n / (2 nseg)), 2);  windows = max(n - k, 0)
+ *   pk_err = #{i < windows: (pos_h(i) == pos_h(i+k)) != (pos_t(i) == pos_t(i+k))}
+ *   wd_err = #{i < windows: pos_h(i+k) - pos_h(i) != pos_t(i+k) - pos_t(i)}
+ *   tp / fp / fn over i < n of h' against t', where t' = t with t'_{n-1} = 0 (compute_Pk leaves it so before f1_score runs) and
+ *   h' = h, with h'_{n-1} = 0 when end_boundary.
+ * n == 0 gives six zeros.  One launch, no workspace, no atomics: integers, identical from run to run.
+ * MTS_ERR_INVALID before any device work for null operands, n_out outside 1..4, T outside 1..64, Lt < L;  MTS_ERR_UNSUPPORTED for L > 65536. */
+int mts_threshold_sweep(void* stream, int B, int L, int Lt, int n_out, const float* scores, const float* targets,
+                        const int32_t* lengths, int T, const float* thresholds, int end_boundary, int32_t* counts_out);
 /* scores[r, c] = x[r,:] . w[c,:] + b[c]  (x act dtype [rows, D]; w fp32 [n_out, D]); n_out in 1..4 */
 int mts_head_fwd(void* stream, int dtype, int rows, int D, int n_out, const void* x, int ldx, const float* w,
                  const float* b, float* scores);

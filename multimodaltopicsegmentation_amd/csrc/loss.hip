@@ -130,20 +130,7 @@ __global__ __launch_bounds__(256) void greedy_decode_kernel(int B, int L, int n_
   const int r = blockIdx.x * 256 + threadIdx.x;
   if (r >= B * L) return;
   const int b = r / L, i = r % L;
-  float p;
-  if (n_out == 1) p = sigmoid_f(scores[r]);                                   // CRF.py:365
-  else if (n_out > 2) {                                                       // softmax over 3 or 4 tags, class 1 (CRF.py:367)
-    float m = scores[(size_t)r * n_out];
-    for (int c = 1; c < n_out; ++c) m = fmaxf(m, scores[(size_t)r * n_out + c]);
-    float se = 0.f;
-    for (int c = 0; c < n_out; ++c) se += expf(scores[(size_t)r * n_out + c] - m);
-    p = expf(scores[(size_t)r * n_out + 1] - m) / se;
-  } else {                                                                    // softmax(...)[..., 1]  CRF.py:367
-    const float x0 = scores[(size_t)r * 2], x1 = scores[(size_t)r * 2 + 1];
-    const float m = fmaxf(x0, x1);
-    const float e0 = expf(x0 - m), e1 = expf(x1 - m);
-    p = e1 / (e0 + e1);
-  }
+  const float p = decode_prob(scores, (size_t)r, n_out);
   const bool valid = i < (lengths ? lengths[b] : L);
   tags[r] = (valid && p > threshold) ? 1 : 0;
 }

@@ -41,3 +41,23 @@ __device__ __forceinline__ float ce2_elem(float x0, float x1, int t, float& g0, 
   g1 = p1 - (t == 1 ? 1.f : 0.f);
   return lse - (t == 0 ? x0 : x1);
 }
+
+// Decode probability of row r of scores [rows, n_out] (models/CRF.py:362-369): sigmoid for one output, softmax class 1 otherwise.  ONE expression
+// for greedy_decode_kernel (loss.hip) and threshold_sweep_kernel (threshold_sweep.hip), so the two take the same decision bit for bit.
+__device__ __forceinline__ float decode_prob(const float* __restrict__ scores, size_t r, int n_out) {
+  float p;
+  if (n_out == 1) p = sigmoid_f(scores[r]);                                   // CRF.py:365
+  else if (n_out > 2) {                                                       // softmax over 3 or 4 tags, class 1 (CRF.py:367)
+    float m = scores[r * n_out];
+    for (int c = 1; c < n_out; ++c) m = fmaxf(m, scores[r * n_out + c]);
+    float se = 0.f;
+    for (int c = 0; c < n_out; ++c) se += expf(scores[r * n_out + c] - m);
+    p = expf(scores[r * n_out + 1] - m) / se;
+  } else {                                                                    // softmax(...)[..., 1]  CRF.py:367
+    const float x0 = scores[r * 2], x1 = scores[r * 2 + 1];
+    const float m = fmaxf(x0, x1);
+    const float e0 = expf(x0 - m), e1 = expf(x1 - m);
+    p = e1 / (e0 + e1);
+  }
+  return p;
+}

@@ -15,6 +15,7 @@ from . import metrics
 from .rnn_taggers import BiLSTM, BiLSTMLateFusion, BiRnnCrf, SheikhBiLSTM, SwitchBiLSTM
 from .t5_taggers import RecurrentLongT5
 from .taggers import Transformer_segmenter
+from .threshold_search import ThresholdSweep
 
 try:  # pragma: no cover - not installed in the build image
     import pytorch_lightning as pl
@@ -116,6 +117,10 @@ class TextSegmenter(_Base):
         self.s_th = search_threshold
         self.metric = metric
         self.best_th, self.losses, self.targets = [], [], []
+        # search_threshold: the validation epoch's device-side sweep (threshold_search.py); None where it does not apply (_sweep_refusal)
+        self._sweep = None
+        if self.s_th and self._sweep_refusal() is None:
+            self._sweep = ThresholdSweep(end_boundary=self.eb, invert=isinstance(self.model, SheikhBiLSTM))
         self.zero_base = zero_baseline
         self.all = bool(all_results)
         if self.all:
@@ -138,6 +143,8 @@ class TextSegmenter(_Base):
         sentence, target, lengths = self._sentence(batch), batch['tgt_tokens'], batch['src_lengths']
         segments = batch['src_segments'] if self.cos else None
         self.best_th, self.losses, self.targets = [], [], []
+        if self._sweep is not None:
+            self._sweep.reset()
         if self.domain:
             domain = batch['domain']
             try:
@@ -171,6 +178,8 @@ class TextSegmenter(_Base):
             for index, score in enumerate(scores):
                 self.losses.append(score[:lengths[index]].detach().cpu().numpy())
                 self.targets.append(target[index][:lengths[index]].detach().cpu().numpy())
+            if self._sweep is not None:
+                self._sweep.add(scores, target, lengths)                     # one launch; the counts stay on the device until the epoch ends
             return None
         with torch.no_grad():
             if self.domain:
@@ -181,6 +190,29 @@ class TextSegmenter(_Base):
                 loss = self.model.loss(sentence, lengths, target)
         self.log_dict({'val_loss': loss, 'threshold': 0.5})
         return loss
+
+    def _sweep_refusal(self):
+        """Why the threshold sweep does not apply to this model, or None."""
+        if isinstance(self.model, BiRnnCrf):
+            return "search_threshold: architecture 'biLSTMCRF' decodes by Viterbi and has no decision threshold to search"
+        if self.metric.lower() in ('b', 'scaiano'):
+            return f"search_threshold: metric '{self.metric}' (B-measure / WinPR) is not in the threshold-sweep kernel; use 'Pk', 'WD' or 'F1'"
+        return None
+
+    # ---- lightning_model.py:435-553 (upstream renamed the hook away; see threshold_search.py for the deviations) ----------
+    def on_validation_epoch_end(self):
+        if not self.s_th:
+            return None
+        why = self._sweep_refusal()
+        if why is not None:
+            raise NotImplementedError(why)
+        results = self._sweep.best(self.metric)
+        self.best_th = results['threshold']
+        self.log_dict(results, on_epoch=True, prog_bar=True)
+        # what configure_optimizers' monitor and upstream's checkpoint file name read
+        self.log('val_loss', results['valid_loss'], on_epoch=True, prog_bar=True)
+        self._sweep.reset()
+        return results
 
     # ---- lightning_model.py:558-676 -------------------------------------------------------------------
     def test_step(self, batch, batch_idx):

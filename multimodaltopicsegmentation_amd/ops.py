@@ -521,6 +521,20 @@ def greedy_decode(scores, lengths, threshold, tags_out):
     check(lib.mts_greedy_decode(stream_ptr(), B, Lq, n_out, ptr(scores), ptr(lengths), float(threshold), ptr(tags_out)))
 
 
+def threshold_sweep(scores, targets, lengths, thresholds, counts_out, end_boundary=False):
+    """counts_out int32 [B, T, 6] = {pk_err, wd_err, windows, tp, fp, fn} of every document x threshold (include/mts.h): scores fp32
+    [B, L, n_out], targets fp32 [B, Lt >= L], lengths int32 [B] or None, thresholds fp32 [T] on the device.  The decision is
+    greedy_decode's ``prob > threshold``, bit for bit."""
+    B, Lq, n_out = scores.shape
+    T = thresholds.numel()
+    assert scores.dtype == torch.float32 and targets.dtype == torch.float32 and thresholds.dtype == torch.float32
+    assert scores.is_contiguous() and targets.is_contiguous() and thresholds.is_contiguous() and targets.shape[0] == B
+    assert lengths is None or (lengths.dtype == torch.int32 and lengths.numel() == B and lengths.is_contiguous())
+    assert counts_out.dtype == torch.int32 and counts_out.is_contiguous() and counts_out.numel() == B * T * 6
+    check(lib.mts_threshold_sweep(stream_ptr(), B, Lq, targets.shape[1], n_out, ptr(scores), ptr(targets), ptr(lengths), T, ptr(thresholds),
+                                  int(bool(end_boundary)), ptr(counts_out)))
+
+
 def head_fwd(x, w, b, scores):
     rows, D = x.shape
     check(lib.mts_head_fwd(stream_ptr(), dtype_code(x.dtype), rows, D, w.shape[0], ptr(x), x.stride(0), ptr(w), ptr(b), ptr(scores)))
