@@ -142,6 +142,26 @@ int mts_cast_concat(void* stream, int dst_dtype, size_t rows, int D1, int D2, co
  * memory: the batch is then ready for an asynchronous host-to-device copy as it stands (prefetch.DevicePrefetcher sends it unstaged). */
 int mts_collate_pad(int src_dtype, int dst_dtype, int B, int Lmax, int D, const void* const* docs, const int64_t* doc_rows, void* dst,
                     float pad_value, int nthreads);
+/* DEVICE-SIDE COLLATION from a corpus resident in HBM (resident.ResidentCorpus): the same batch as mts_collate_pad, gathered by a list
+ * of document indices, so that a training step needs neither a host pass nor a host-to-device copy of the batch.
+ *   dst[b, i, :] = corpus[row_start[d] + i, :]  for i < min(row_start[d + 1] - row_start[d], Lmax),  d = doc_index[b];
+ *   every other element of dst = pad_value.  The kernel writes EVERY element of dst (no memset in front of it).
+ * F32 -> F32 and BF16 -> BF16 copy bits; F32 -> BF16 rounds to nearest even and keeps a NaN quiet (sign and high payload kept, quiet
+ * bit set: the bits of mts_collate_pad and of torch's .to(torch.bfloat16) on the device; torch's HOST conversion agrees on everything
+ * but a NaN, for which its vector loop and its scalar tail give different bits); BF16 -> F32 is MTS_ERR_UNSUPPORTED.  The targets take the same entry point with D = 1, F32 -> F32
+ * and pad_value -1 or 0.  All element offsets are 64-bit (B * Lmax * D may exceed 2^31).  A doc_index outside 0 .. n_docs - 1 gives an
+ * all-pad document and no address is formed from it; row_start itself is trusted (ascending, row_start[n_docs] = total_rows).
+ * One launch, plain vector stores, no atomics, no workspace; 16-byte accesses when the row's byte length and both base addresses are
+ * multiples of 16, exact narrower ones otherwise (D = 770 in fp32, D = 1).  corpus and dst aligned to their element size.
+ * MTS_ERR_INVALID before any device work: unknown dtypes, B < 0, Lmax < 1, D < 1, n_docs < 1, and with B > 0 a null corpus, row_start,
+ * doc_index or dst.  B == 0 returns MTS_OK without a launch. */
+int mts_gather_pad(void* stream, int src_dtype, int dst_dtype, int B, int Lmax, int D,
+                   const void* corpus,          /* device [total_rows, D], row-major, contiguous */
+                   const int64_t* row_start,    /* device [n_docs + 1], ascending, row_start[0] = 0 */
+                   int n_docs,
+                   const int32_t* doc_index,    /* device [B], repeats allowed */
+                   void* dst,                   /* device [B, Lmax, D] in dst_dtype */
+                   float pad_value);
 
 /* ---------------------------------------------------------------------------------------------
  * LayerNorm family (biased variance, eps inside sqrt).

@@ -120,6 +120,7 @@ SIGNATURES = {
     'mts_sgd_step_clipped': (_i, [_vp, _sz, _vp, _vp, _vp, _f, _f, _f, _i, _f, _vp, _vp, _f, _f, _vp]),
     'mts_scale': (_i, [_vp, _sz, _vp, _f]),
     'mts_collate_pad': (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _f, _i]),
+    'mts_gather_pad': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _f]),
 }
 
 _missing = []

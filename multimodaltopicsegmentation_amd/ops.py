@@ -197,6 +197,22 @@ def cast_concat(x1, x2, dst):
     return dst
 
 
+def gather_pad(corpus, row_start, doc_index, dst, pad_value=0.0):
+    """dst [B, Lmax, D] (or [B, Lmax] from a 1-d corpus: the targets) = the padded batch of documents ``doc_index`` (int32 [B], on the
+    device) of a device-resident corpus [total_rows, D] whose document d is rows row_start[d] .. row_start[d + 1] (int64 [n_docs + 1],
+    on the device): include/mts.h mts_gather_pad.  Every element of dst is written; an index outside the corpus gives an all-pad
+    document.  fp32 -> fp32, bf16 -> bf16 or fp32 -> bf16 (round to nearest even)."""
+    B, Lmax = int(dst.shape[0]), int(dst.shape[1])
+    D = 1 if corpus.dim() == 1 else int(corpus.shape[1])
+    assert dst.numel() == B * Lmax * D and dst.is_contiguous() and corpus.is_contiguous()
+    assert row_start.dtype == torch.int64 and row_start.is_contiguous() and row_start.numel() >= 2
+    assert doc_index.dtype == torch.int32 and doc_index.is_contiguous() and doc_index.numel() == B
+    assert corpus.device == dst.device == row_start.device == doc_index.device
+    check(lib.mts_gather_pad(stream_ptr(), dtype_code(corpus.dtype), dtype_code(dst.dtype), B, Lmax, D, ptr(corpus), ptr(row_start),
+                             row_start.numel() - 1, ptr(doc_index), ptr(dst), float(pad_value)))
+    return dst
+
+
 def embed_layernorm_fwd(x, pos, pos_offset, type0, gamma, beta, eps, y, pre, mean, rstd, row_src=None, x2=None):
     """row_src (int32 [n_rows], optional): packed batch -- output row r is sentence row_src[r] = b*L + i of x.
     x2 (fp32 [B, L, D2], optional): K-split input -- the row is x[b, i] | x2[b, i] and the concatenation is never materialised."""

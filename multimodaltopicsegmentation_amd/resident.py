@@ -1,0 +1,237 @@
+"""The corpus lives in HBM: batches are GATHERED on the device, and every data-parallel rank gathers only its own documents.
+
+The corpora this tagger trains on are tiny next to the memory of the card (RadioNews: 55 documents, 33 179 sentences -- 119 MB in bf16
+at D = 1792, 238 MB in fp32, against 288 GB), so the fastest host collater is no host collater:
+
+  * ``ResidentCorpus(dataset, device)`` concatenates the documents of an ``AudioPortionDataset`` (any mode: early or late fusion,
+    domains, segments, truncate on or off, CRF pad) into one [total_rows, D] device tensor per input plus a [total_rows] fp32 tensor of
+    targets, uploaded ONCE;
+  * ``corpus.batch(indices, pad_to=None)`` returns the batch dict a collated batch has after ``DevicePrefetcher``: ``src_tokens``,
+    ``src_tokens2`` (or None) and ``tgt_tokens`` built on the device by ``ops.gather_pad`` (csrc/gather.hip: one launch per tensor on the
+    current stream, every element written, no memset), ``src_lengths`` (int64), ``id``, ``domain`` and ``src_segments`` on the host
+    from tables made at construction.  The only per-call transfer is one asynchronous copy of the B int32 indices out of a small
+    pinned ring; nothing synchronises and nothing pageable is copied.  In fp32 the tensors are ``torch.equal`` to
+    ``dataset.collater([dataset[i] for i in indices])`` (the reference path, EncoderDataset.py:91-152) moved to the device, with
+    ``wire_dtype='bf16'`` the embeddings equal that batch's ``.to(torch.bfloat16)``; repeats in ``indices`` are allowed;
+  * ``DocumentShardSampler(lengths, batch_size, rank, world)`` yields ``(local_indices, pad_to)`` per global batch: the documents
+    ``global_batch[rank::world]`` (the rule of ``trainer.shard_batch``) and the longest document of the WHOLE global batch, computed from
+    the host length table -- every rank pads to the same length without a collective, so ``NativeTrainer._check_same_length`` passes
+    and no rank collates documents it then throws away.
+
+For every tagger but ``SwitchBiLSTM(switch='dense')`` (see ``trainer.shard_batch``), ``corpus.batch(*item)`` on rank r holds the bits of
+``shard_batch(collated global batch, r, world)``.  ``NativeTrainer.step`` takes these batches as they are.
+"""
+import numpy as np
+import torch
+
+_WIRE = {'fp32': torch.float32, 'bf16': torch.bfloat16}
+_RING_SLOTS = 16
+
+
+def _rows_2d(items, what):
+    """documents -> list of contiguous fp32 / bf16 [rows, D] host tensors of one width"""
+    out = []
+    for k, e in enumerate(items):
+        t = torch.as_tensor(e)
+        if t.dim() != 2:
+            raise ValueError(f'ResidentCorpus: {what} of document {k} is {t.dim()}-d; [sentences, D] matrices are expected')
+        out.append(t)
+    widths = {int(t.shape[1]) for t in out}
+    if len(widths) > 1:
+        raise ValueError(f'ResidentCorpus: {what} widths differ between documents: {sorted(widths)}')
+    return out
+
+
+class ResidentCorpus:
+    def __init__(self, dataset, device, wire_dtype=None, segments=None):
+        """dataset: an AudioPortionDataset; wire_dtype: 'fp32' | 'bf16' | None (the dataset's own); segments: add 'src_segments' to the
+        batches (None: as the dataset does)."""
+        if wire_dtype is None:
+            wire_dtype = 'bf16' if getattr(dataset, 'wire', torch.float32) == torch.bfloat16 else 'fp32'
+        if wire_dtype not in _WIRE:
+            raise ValueError("wire_dtype must be 'fp32' or 'bf16'")
+        self.wire = _WIRE[wire_dtype]
+        self.device = torch.device(device)
+        if self.device.type == 'cuda' and self.device.index is None:
+            self.device = torch.device('cuda', torch.cuda.current_device())
+        self.truncate, self.tv, self.minus = bool(dataset.truncate), int(dataset.tv), int(dataset.minus)
+        self.segments = bool(dataset.segments if segments is None else segments)
+        self.da = bool(dataset.da)
+        self.domain = list(dataset.domain)
+        if len(dataset) == 0:
+            raise ValueError('ResidentCorpus: the dataset has no documents')
+        emb = _rows_2d(dataset.embeddings, 'embeddings')
+        emb2 = _rows_2d(dataset.embeddings2, 'second-input embeddings') if dataset.embeddings2 else None
+        tgt = [torch.as_tensor(t).to(torch.float32).reshape(-1) for t in dataset.tgt_dataset]
+        rows = np.array([int(t.shape[0]) for t in emb], dtype=np.int64)
+        for k, t in enumerate(tgt):
+            if int(t.shape[0]) != rows[k]:
+                raise ValueError(f'ResidentCorpus: document {k} has {int(rows[k])} sentences but {int(t.shape[0])} targets')
+        if emb2 is not None and (len(emb2) != len(emb) or any(int(t.shape[0]) != rows[k] for k, t in enumerate(emb2))):
+            raise ValueError('ResidentCorpus: the second input does not have the first input\'s sentences per document')
+        self.n_docs = len(emb)
+        self.rows = rows                                                           # sentences per document, as stored
+        self.lengths = np.minimum(rows, self.tv) if self.truncate else rows.copy()  # what a batch reports as src_lengths
+        start = np.zeros(self.n_docs + 1, dtype=np.int64)
+        np.cumsum(rows, out=start[1:])
+        self.total_rows = int(start[-1])
+        # per-document segment ends, what AudioPortionDataset._segments_of makes from the collated batch: the positions just behind
+        # the boundary sentences inside the reported length
+        self._segment_ends = [(np.flatnonzero(t.numpy()[:int(n)] == 1) + 1).tolist() for t, n in zip(tgt, self.lengths)] if self.segments else None
+
+        def upload(docs):
+            # fp32 first: the values the reference's `merge` writes into its fp32 batch; bf16 is that batch's .to(torch.bfloat16)
+            return torch.cat([t.to(torch.float32) for t in docs]).to(self.wire).contiguous().to(self.device)
+        self.corpus = upload(emb)
+        self.corpus2 = upload(emb2) if emb2 is not None else None
+        self.targets = torch.cat(tgt).contiguous().to(self.device)
+        self.row_start = torch.from_numpy(start).to(self.device)
+        self._ring = None
+        self._turn = 0
+
+    def __len__(self):
+        return self.n_docs
+
+    @property
+    def nbytes(self):
+        """bytes of the resident data (embeddings, second input, targets, row table)"""
+        return sum(t.numel() * t.element_size() for t in (self.corpus, self.corpus2, self.targets, self.row_start) if t is not None)
+
+    def sampler(self, batch_size, **kw):
+        """a DocumentShardSampler over this corpus (with truncate=True every batch is truncate_value long: no pad_to)"""
+        return DocumentShardSampler(self.n_docs if self.truncate else self.lengths, batch_size, **kw)
+
+    # ---- host half ---------------------------------------------------------------------------------------------------------
+    def _indices(self, indices):
+        ii = np.asarray(indices, dtype=np.int64).reshape(-1)
+        if ii.size and (int(ii.min()) < 0 or int(ii.max()) >= self.n_docs):
+            raise IndexError(f'ResidentCorpus: document index outside 0 .. {self.n_docs - 1}')
+        return ii
+
+    def _padded_length(self, ii, pad_to):
+        if self.truncate:
+            if pad_to is not None:
+                raise ValueError('pad_to cannot be combined with truncate=True (every batch is truncate_value long)')
+            return self.tv
+        longest = int(self.rows[ii].max())
+        if pad_to is None:
+            return longest
+        if int(pad_to) < longest:
+            raise ValueError(f'pad_to {int(pad_to)} is shorter than the longest listed document ({longest})')
+        return int(pad_to)
+
+    def _host_fields(self, ii, pad_to):
+        Lmax = self._padded_length(ii, pad_to)
+        idx = ii.tolist()
+        out = {'id': torch.from_numpy(ii.copy()), 'src_lengths': torch.from_numpy(self.lengths[ii].astype(np.int64, copy=True)),
+               'domain': [self.domain[i] for i in idx] if self.da else None}
+        if self.segments:
+            out['src_segments'] = [list(self._segment_ends[i]) for i in idx]
+        return out, Lmax
+
+    def host_fields(self, indices, pad_to=None):
+        """-> ({'id', 'src_lengths', 'domain'(, 'src_segments')}, padded length) of the batch of documents ``indices``: the host half
+        of ``batch()``; touches no GPU.  An empty list gives ({}, 0)."""
+        ii = self._indices(indices)
+        if ii.size == 0:
+            return {}, 0
+        return self._host_fields(ii, pad_to)
+
+    # ---- device half -------------------------------------------------------------------------------------------------------
+    def _upload_indices(self, ii):
+        """the B indices as an int32 device tensor: written into a slot of a pinned ring, one asynchronous copy on the current stream.
+        A slot is written again _RING_SLOTS calls later; its copy's event is waited for only if the device is that far behind."""
+        B = ii.size
+        if self._ring is None:
+            self._ring = [[None, None] for _ in range(_RING_SLOTS)]
+        slot = self._ring[self._turn % _RING_SLOTS]
+        self._turn += 1
+        if slot[0] is None or slot[0].numel() < B:
+            slot[0] = torch.empty(max(B, 64), dtype=torch.int32).pin_memory()
+            slot[1] = torch.cuda.Event()
+        elif not slot[1].query():
+            slot[1].synchronize()
+        slot[0].numpy()[:B] = ii
+        dev = torch.empty(B, dtype=torch.int32, device=self.device)
+        dev.copy_(slot[0][:B], non_blocking=True)
+        slot[1].record()
+        return dev
+
+    def batch(self, indices, pad_to=None):
+        """the batch dict of documents ``indices`` (module docstring).  {} for an empty list; IndexError for an index outside the corpus;
+        ValueError for a pad_to below the longest listed document or together with truncate=True."""
+        ii = self._indices(indices)
+        if ii.size == 0:
+            return {}
+        out, Lmax = self._host_fields(ii, pad_to)
+        if self.device.type != 'cuda':
+            raise RuntimeError('ResidentCorpus.batch gathers on the GPU (there is no CPU fallback); host_fields() is the part that needs none')
+        from . import ops
+        with torch.cuda.device(self.device):
+            B = int(ii.size)
+            idx = self._upload_indices(ii)
+            out['src_tokens'] = ops.gather_pad(self.corpus, self.row_start, idx,
+                                               torch.empty((B, Lmax, self.corpus.shape[1]), dtype=self.wire, device=self.device))
+            out['src_tokens2'] = None if self.corpus2 is None else ops.gather_pad(
+                self.corpus2, self.row_start, idx, torch.empty((B, Lmax, self.corpus2.shape[1]), dtype=self.wire, device=self.device))
+            # pad -1, or 0 for the CRF head (EncoderDataset.py:23)
+            out['tgt_tokens'] = ops.gather_pad(self.targets, self.row_start, idx, torch.empty((B, Lmax), dtype=torch.float32, device=self.device),
+                                               pad_value=0.0 - self.minus)
+        return out
+
+
+class DocumentShardSampler:
+    """Rank-local batch sampler for data-parallel training from a ResidentCorpus.
+
+    ``lengths``: sentences per document (ResidentCorpus.lengths), or just the number of documents -- ``pad_to`` is then None, what a
+    truncate=True corpus wants.  ``batch_size`` is the GLOBAL batch size.  Iterating yields ``(local_indices, pad_to)`` per global
+    batch: ``global_batch[rank::world]`` and the longest document of the whole global batch.  Every rank with the same seed and epoch
+    (``set_epoch``) draws the same permutation, so ``len()`` and ``pad_to`` agree on every rank without a collective.  The last, smaller
+    global batch is kept unless ``drop_last``; a global batch with fewer documents than ``world`` is dropped on EVERY rank (a rank
+    without documents cannot take part in the step's collectives): ``dropped_documents`` counts those.  world == 1: a plain batch
+    sampler, pad_to = the batch's own maximum."""
+
+    def __init__(self, lengths, batch_size, rank=0, world=1, shuffle=True, seed=0, drop_last=False):
+        if isinstance(lengths, (int, np.integer)):
+            self.n, self.lengths = int(lengths), None
+        else:
+            self.lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+            self.n = int(self.lengths.size)
+        self.batch_size, self.rank, self.world = int(batch_size), int(rank), int(world)
+        if self.batch_size < 1 or self.world < 1 or not 0 <= self.rank < self.world:
+            raise ValueError('DocumentShardSampler: need batch_size >= 1, world >= 1 and 0 <= rank < world')
+        self.shuffle, self.seed, self.drop_last, self.epoch = bool(shuffle), int(seed), bool(drop_last), 0
+        full, rest = divmod(self.n, self.batch_size)
+        self._n_batches, self.dropped_documents = full, 0
+        if full and self.batch_size < self.world:                  # every global batch is too small to give each rank a document
+            self._n_batches, self.dropped_documents = 0, full * self.batch_size
+        if rest and not self.drop_last:
+            if rest >= self.world:
+                self._n_batches += 1
+            else:
+                self.dropped_documents += rest
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+
+    def __len__(self):
+        return self._n_batches
+
+    def permutation(self):
+        """the epoch's document order: the same on every rank"""
+        if not self.shuffle:
+            return np.arange(self.n, dtype=np.int64)
+        return np.random.default_rng([self.seed, self.epoch]).permutation(self.n).astype(np.int64)
+
+    def global_batches(self):
+        perm = self.permutation()
+        for k in range(0, self.n, self.batch_size):
+            g = perm[k:k + self.batch_size]
+            if g.size < self.world or (self.drop_last and g.size < self.batch_size):
+                continue
+            yield g
+
+    def __iter__(self):
+        for g in self.global_batches():
+            pad_to = int(self.lengths[g].max()) if self.lengths is not None else None
+            yield g[self.rank::self.world].tolist(), pad_to

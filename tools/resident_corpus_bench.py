@@ -1,0 +1,180 @@
+#!/usr/bin/env python3
+"""What the device-resident corpus costs and what it saves (resident.ResidentCorpus, csrc/gather.hip; DESIGN.md §3 "Device-resident
+corpus").  One process, every leg warmed, the legs taken IN TURN so that a drift of the machine hits all of them; REPS repetitions,
+the report gives each repetition and the spread.
+
+(a) the gather alone, every call between two device events, at BASELINE configs[1]'s batch 64 x 256 x 1792: equal lengths (256) and
+    ragged lengths U{64..256} padded to 256, bf16 -> bf16 and fp32 -> bf16, out of a corpus of 256 documents with a fresh random index
+    list per call.  Rate = (bytes read + bytes written) / time, next to a device copy (torch's copy_ kernel) of the same batch bytes and
+    next to the repository's own Adam kernel (30 bytes per element with the bf16 mirror) in the same loop.
+(b) NativeTrainer.step of the configs[1] transformer (bf16), a host clock round windows of steps that end in a synchronise, fed by
+    (i)   one fixed batch resident in HBM, fp32 (bench.py's `value`), and (i') the same in bf16;
+    (ii)  AudioPortionDataset(pin_memory=True, wire_dtype='bf16') -> DevicePrefetcher: the fastest pipeline without a resident corpus;
+    (iii) ResidentCorpus(wire_dtype='bf16') + DocumentShardSampler: a new batch gathered on the device every step.
+
+  python tools/resident_corpus_bench.py [--out profiles/resident_corpus_bench.txt] [--iters 200] [--steps 150] [--reps 3]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from multimodaltopicsegmentation_amd import AudioPortionDataset, DevicePrefetcher, ResidentCorpus, ops  # noqa: E402
+from multimodaltopicsegmentation_amd.taggers import Transformer_segmenter  # noqa: E402
+from multimodaltopicsegmentation_amd.trainer import NativeTrainer  # noqa: E402
+
+B, L, D, N_DOCS = 64, 256, 1792, 256
+ADAM_N, ADAM_BYTES = 16 * 2 ** 20, 30
+DEV = 'cuda'
+
+
+def median(v):
+    v = sorted(v)
+    return v[len(v) // 2]
+
+
+def gather_legs(iters, reps, say):
+    g = torch.Generator().manual_seed(1)
+    lengths = {'equal': torch.full((N_DOCS,), L, dtype=torch.int64), 'ragged': torch.randint(64, L + 1, (N_DOCS,), generator=g)}
+    legs, nbytes = {}, {}
+    for shape, ln in lengths.items():
+        start = torch.zeros(N_DOCS + 1, dtype=torch.int64)
+        start[1:] = ln.cumsum(0)
+        total = int(start[-1])
+        row_start = start.to(DEV)
+        for src in (torch.bfloat16, torch.float32):
+            corpus = torch.randn(total, D, device=DEV, dtype=torch.float32).to(src)
+            dst = torch.empty(B, L, D, dtype=torch.bfloat16, device=DEV)
+            lists = torch.randint(0, N_DOCS, (iters + 8, B), generator=g)
+            idx_dev = lists.to(torch.int32).to(DEV)
+            name = f'gather {"bf16" if src == torch.bfloat16 else "fp32"} -> bf16, {shape}'
+            read = ln[lists].sum(1).double().mean().item() * D * corpus.element_size()         # mean over the index lists
+            nbytes[name] = read + B * L * D * 2
+            legs[name] = (lambda k, c=corpus, r=row_start, i=idx_dev, d=dst: ops.gather_pad(c, r, i[k % i.shape[0]], d))
+    a16, b16 = torch.randn(B, L, D, device=DEV).to(torch.bfloat16), torch.empty(B, L, D, dtype=torch.bfloat16, device=DEV)
+    a32 = torch.randn(B, L, D, device=DEV)
+    legs['device copy bf16 -> bf16'] = lambda k: b16.copy_(a16)
+    nbytes['device copy bf16 -> bf16'] = 2 * B * L * D * 2
+    legs['device copy fp32 -> bf16'] = lambda k: b16.copy_(a32)
+    nbytes['device copy fp32 -> bf16'] = B * L * D * 6
+    p, gr, m, v = (torch.randn(ADAM_N, device=DEV) * s for s in (1.0, 1e-3, 1e-3, 0.0))
+    v.abs_()
+    mirror = torch.empty(ADAM_N, dtype=torch.bfloat16, device=DEV)
+    legs['adam_step (16 Mi elements, bf16 mirror)'] = lambda k: ops.adam_step(p, gr, m, v, 1e-3, 0.9, 0.999, 1e-7, k + 1, 1.0, mirror)
+    nbytes['adam_step (16 Mi elements, bf16 mirror)'] = ADAM_BYTES * ADAM_N
+    for k in range(8):                                                                      # warm every leg
+        for f in legs.values():
+            f(k)
+    torch.cuda.synchronize()
+    out = {name: [] for name in legs}
+    for _ in range(reps):
+        ev = {name: [] for name in legs}
+        for k in range(iters):
+            for name, f in legs.items():
+                s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                s.record()
+                f(k)
+                e.record()
+                ev[name].append((s, e))
+        torch.cuda.synchronize()
+        for name in legs:
+            out[name].append(median([s.elapsed_time(e) * 1e3 for s, e in ev[name]]))
+    say(f'(a) one call between two device events, median of {iters} per repetition, the legs in turn; batch {B} x {L} x {D}')
+    res = {}
+    for name, us in out.items():
+        rates = [nbytes[name] / (t * 1e-6) / 1e12 for t in us]
+        say(f'  {name:42s} {nbytes[name] / 1e6:7.1f} MB   ' + '  '.join(f'{t:7.1f} us' for t in us) + '   ' + '  '.join(f'{r:5.2f}' for r in rates) + ' TB/s')
+        res[name] = {'MB': round(nbytes[name] / 1e6, 1), 'us': [round(t, 1) for t in us], 'TBps': [round(r, 3) for r in rates]}
+    return res
+
+
+def step_legs(steps, warmup, reps, say):
+    def model():
+        return Transformer_segmenter(2, D, 256, num_layers=1, nheads=8, loss_fn='FocalLoss', window_size=30, compute_dtype='bf16', seed=1234).to(DEV)
+    g = torch.Generator().manual_seed(4321)
+    lines = [(torch.randn(L, D, generator=g), (torch.rand(L, generator=g) < 0.05).float().tolist(), f'doc{i}') for i in range(N_DOCS)]
+    ds = AudioPortionDataset(lines, {'0': 0, '1': 1}, CRF=False, truncate=False, pin_memory=True, wire_dtype='bf16', pin_slots=4,
+                             collate_threads=min(16, os.cpu_count() or 8))
+    corpus = ResidentCorpus(ds, DEV, wire_dtype='bf16')
+    sampler = corpus.sampler(B, seed=9)
+    epoch = [0]
+
+    def index_lists(n):
+        got = 0
+        while got < n:
+            sampler.set_epoch(epoch[0])
+            epoch[0] += 1
+            for ix, pad_to in sampler:
+                if got < n:
+                    got += 1
+                    yield ix, pad_to
+    fixed = ds.collater(ds.__getitems__(list(range(B))))
+    fixed16 = {k: (v.to(DEV) if isinstance(v, torch.Tensor) and v.is_floating_point() else v) for k, v in fixed.items()}
+    fixed32 = dict(fixed16, src_tokens=fixed16['src_tokens'].float())
+    torch.cuda.synchronize()
+    trainers = {name: NativeTrainer(model(), lr=1e-3, optimizer='Adam') for name in ('i', "i'", 'ii', 'iii')}
+
+    def feed(name, n):
+        if name == 'i':
+            return (fixed32 for _ in range(n))
+        if name == "i'":
+            return (fixed16 for _ in range(n))
+        if name == 'ii':
+            return DevicePrefetcher((ds.collater(ds.__getitems__(ix)) for ix, _ in index_lists(n)), DEV, depth=2)
+        return (corpus.batch(ix, pad_to) for ix, pad_to in index_lists(n))
+    label = {'i': '(i)   fixed resident batch, fp32', "i'": "(i')  fixed resident batch, bf16",
+             'ii': '(ii)  pinned bf16 collater -> DevicePrefetcher', 'iii': '(iii) ResidentCorpus(bf16) + sampler'}
+    ms = {name: [] for name in trainers}
+    for _ in range(reps):
+        for name, tr in trainers.items():
+            t0 = None
+            for k, batch in enumerate(feed(name, warmup + steps)):
+                if k == warmup:
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                tr.step(batch)
+            torch.cuda.synchronize()
+            ms[name].append(1e3 * (time.perf_counter() - t0) / steps)
+    say(f'(b) NativeTrainer.step, configs[1] transformer bf16 at {B} x {L} x {D}: ms per step over windows of {steps} steps '
+        f'({warmup} warm-up steps each), the legs in turn, {reps} repetitions; corpus {N_DOCS} documents, {corpus.nbytes / 1e6:.0f} MB resident')
+    for name in trainers:
+        say(f'  {label[name]:48s} ' + '  '.join(f'{t:.4f}' for t in ms[name]) + f'   median {median(ms[name]):.4f}  spread {max(ms[name]) - min(ms[name]):.4f}')
+    d_ii = [a - b for a, b in zip(ms['iii'], ms['ii'])]
+    d_i = [a - b for a, b in zip(ms['iii'], ms['i'])]
+    d_i16 = [a - b for a, b in zip(ms['iii'], ms["i'"])]
+    say('  (iii) - (ii)  per repetition: ' + '  '.join(f'{1e3 * d:+.1f} us' for d in d_ii))
+    say('  (iii) - (i)   per repetition: ' + '  '.join(f'{1e3 * d:+.1f} us' for d in d_i))
+    say("  (iii) - (i')  per repetition: " + '  '.join(f'{1e3 * d:+.1f} us' for d in d_i16))
+    return {k: [round(t, 4) for t in v] for k, v in ms.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--out', default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'resident_corpus_bench.txt'))
+    ap.add_argument('--iters', type=int, default=200)
+    ap.add_argument('--steps', type=int, default=150)
+    ap.add_argument('--warmup', type=int, default=15)
+    ap.add_argument('--reps', type=int, default=3)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit('resident_corpus_bench: no GPU visible; nothing is measured without one')
+    lines = []
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+    say(f'tools/resident_corpus_bench.py --iters {a.iters} --steps {a.steps} --warmup {a.warmup} --reps {a.reps}   ({torch.cuda.get_device_name(0)})')
+    res = {'gather': gather_legs(a.iters, a.reps, say)}
+    res['step_ms'] = step_legs(a.steps, a.warmup, a.reps, say)
+    say(json.dumps(res))
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, 'w') as f:
+        f.write('\n'.join(lines) + '\n')
+
+
+if __name__ == '__main__':
+    main()
