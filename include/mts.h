@@ -525,12 +525,21 @@ int mts_lstm_bwd_whh(void* stream, int dtype, int B, int L, int H, int ndir, con
  * CRF head.  Replaces models/CRF.py:98-240 (fc output = `feats` is produced by mts_gemm/mts_head_fwd).
  * feats: fp32 [B, L, C]; C = num_tags + 2 (START = C-2, STOP = C-1); trans fp32 [C, C], T[i,j] = j -> i.
  * ------------------------------------------------------------------------------------------- */
-/* loss_out[0] = mean_b(logZ_b - gold_b); dfeats [B,L,C] and dtrans [C,C] are OVERWRITTEN (may be NULL). */
+/* loss_out[0] = mean_b(logZ_b - gold_b); dfeats [B,L,C] and dtrans [C,C] are OVERWRITTEN (may be NULL; dtrans needs dfeats).
+ * C in 3..8; lengths may be NULL (every document L long) and are clamped to 0..L; tags fp32 [B, Lt], Lt >= L; rows of dfeats past a
+ * document's length are written 0.
+ * Numeric domain of C == 4: that path carries softmax(alpha) in fp32 (the scaled recursion), so a step's worst filtered-probability
+ * ratio exp(-(2 Se + 2 St)) -- Se, St: the largest |emission| and |finite transition| -- must stay a normal fp32: emission spread
+ * plus transition spread below about 87 nats per step.  Beyond that a tag's probability underflows to 0 and dfeats / dtrans can be
+ * wrong WITHOUT a NaN or an error code (the loss degrades later than the gradients).  The generic path (C != 4) works in the log
+ * domain and has no such limit.  Evidence so far: an fp32 CPU emulation of the recursion (exact at +-30 / +-10 and +-40 / +-20,
+ * dfeats off by 1.0 at +-60 / +-20) and tests/test_gpu_crf.py at +-30 / +-10; the kernel neither detects nor survives that regime. */
 size_t mts_crf_workspace(int B, int L, int C);
 int mts_crf_nll(void* stream, int B, int L, int C, const float* feats, const float* tags, int Lt,
                 const int32_t* lengths, const float* trans, float* loss_out, float* dfeats, float* dtrans,
                 float* workspace /* mts_crf_workspace(B, L, C) bytes */);
-/* best_score fp32 [B]; paths int32 [B, L] (entries >= length undefined); bp_ws int32 [B, L, C] */
+/* best_score fp32 [B]; paths int32 [B, L] (entries >= length are written -1); bp_ws int32 [B, L, C].  Ties go to the lowest tag
+ * index (torch.max).  C == 4 keeps its back-pointers in LDS up to L = 10 240 and uses bp_ws (the generic kernel) beyond. */
 int mts_crf_viterbi(void* stream, int B, int L, int C, const float* feats, const int32_t* lengths,
                     const float* trans, float* best_score, int32_t* paths, int32_t* bp_ws);
 
