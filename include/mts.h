@@ -457,6 +457,19 @@ int mts_greedy_decode(void* stream, int B, int L, int n_out, const float* scores
  * MTS_ERR_INVALID before any device work for null operands, n_out outside 1..4, T outside 1..64, Lt < L;  MTS_ERR_UNSUPPORTED for L > 65536. */
 int mts_threshold_sweep(void* stream, int B, int L, int Lt, int n_out, const float* scores, const float* targets,
                         const int32_t* lengths, int T, const float* thresholds, int end_boundary, int32_t* counts_out);
+/* WinPR SWEEP (metric 'scaiano').  Replaces the host loop over WinPR (models/lightning_model.py:57-124) as test_step calls it (:622),
+ * WinPR(reference = tags, hypothesis = target): operands, ranges and status codes as mts_threshold_sweep, plus the window k, 1..64
+ * (upstream: 10); counts_out int32 [B, T, 3] = {TP, FP, FN}.  For a document of n sentences, h and t as above, except that the masks
+ * are left as the scaiano branch of test_step leaves them: under end_boundary bit n-1 is 0 in BOTH, otherwise nothing is cleared (the
+ * target's last sentence counts, unlike the F1 counts above).  For every i = 1-k .. n (n + k windows) and a in {h, t}:
+ *   cnt(a, i)  = #{x in [max(i,0), min(i+k,n)) : a_x} + prev(a, i)
+ *   prev(a, i) = 0 for i == 1-k;  a[i-1] for i >= 1;  for 2-k <= i <= 0: a[lo] if lo < hi else 0, lo = max(n+i-1, 0), hi = min(i-1+k, n)
+ *                (python's wrap-around of reference[i-1:i-1+k] for a negative start; non-zero only for n < k)
+ *   R = cnt(h, i), C = cnt(t, i);  TP += min(R, C);  FP += max(0, C - R);  FN += max(0, R - C)
+ * n == 0 gives three zeros.  One launch, no workspace, no atomics: integers, identical from run to run.
+ * MTS_ERR_INVALID additionally for k outside 1..64. */
+int mts_winpr_sweep(void* stream, int B, int L, int Lt, int n_out, const float* scores, const float* targets,
+                    const int32_t* lengths, int T, const float* thresholds, int end_boundary, int k, int32_t* counts_out);
 /* scores[r, c] = x[r,:] . w[c,:] + b[c]  (x act dtype [rows, D]; w fp32 [n_out, D]); n_out in 1..4 */
 int mts_head_fwd(void* stream, int dtype, int rows, int D, int n_out, const void* x, int ldx, const float* w,
                  const float* b, float* scores);

@@ -13,7 +13,8 @@ from .rnn_taggers import BiLSTM, BiLSTMLateFusion, BiRnnCrf, SheikhBiLSTM, Switc
 from .t5_taggers import RecurrentLongT5  # noqa: F401
 from .taggers import RestrictedTransformerEncoderLayer, Transformer_segmenter  # noqa: F401
 from .threshold_search import DEFAULT_THRESHOLDS, ThresholdSweep  # noqa: F401
+from .fit import fit  # noqa: F401
 
 __all__ = ['TextSegmenter', 'Transformer_segmenter', 'BiLSTM', 'BiLSTMLateFusion', 'BiRnnCrf', 'RecurrentLongT5', 'SheikhBiLSTM', 'SwitchBiLSTM', 'AudioPortionDataset',
            'AudioPortionDatasetInference', 'RestrictedTransformerEncoderLayer', 'DevicePrefetcher', 'ThresholdSweep', 'DEFAULT_THRESHOLDS', 'ResidentCorpus',
-           'DocumentShardSampler']
+           'DocumentShardSampler', 'fit']

@@ -537,18 +537,32 @@ def greedy_decode(scores, lengths, threshold, tags_out):
     check(lib.mts_greedy_decode(stream_ptr(), B, Lq, n_out, ptr(scores), ptr(lengths), float(threshold), ptr(tags_out)))
 
 
-def threshold_sweep(scores, targets, lengths, thresholds, counts_out, end_boundary=False):
-    """counts_out int32 [B, T, 6] = {pk_err, wd_err, windows, tp, fp, fn} of every document x threshold (include/mts.h): scores fp32
-    [B, L, n_out], targets fp32 [B, Lt >= L], lengths int32 [B] or None, thresholds fp32 [T] on the device.  The decision is
-    greedy_decode's ``prob > threshold``, bit for bit."""
+def _sweep_operands(scores, targets, lengths, thresholds, counts_out, width):
+    """the argument checks the two sweep kernels share -> (B, L, n_out, T)"""
     B, Lq, n_out = scores.shape
     T = thresholds.numel()
     assert scores.dtype == torch.float32 and targets.dtype == torch.float32 and thresholds.dtype == torch.float32
     assert scores.is_contiguous() and targets.is_contiguous() and thresholds.is_contiguous() and targets.shape[0] == B
     assert lengths is None or (lengths.dtype == torch.int32 and lengths.numel() == B and lengths.is_contiguous())
-    assert counts_out.dtype == torch.int32 and counts_out.is_contiguous() and counts_out.numel() == B * T * 6
+    assert counts_out.dtype == torch.int32 and counts_out.is_contiguous() and counts_out.numel() == B * T * width
+    return B, Lq, n_out, T
+
+
+def threshold_sweep(scores, targets, lengths, thresholds, counts_out, end_boundary=False):
+    """counts_out int32 [B, T, 6] = {pk_err, wd_err, windows, tp, fp, fn} of every document x threshold (include/mts.h): scores fp32
+    [B, L, n_out], targets fp32 [B, Lt >= L], lengths int32 [B] or None, thresholds fp32 [T] on the device.  The decision is
+    greedy_decode's ``prob > threshold``, bit for bit."""
+    B, Lq, n_out, T = _sweep_operands(scores, targets, lengths, thresholds, counts_out, 6)
     check(lib.mts_threshold_sweep(stream_ptr(), B, Lq, targets.shape[1], n_out, ptr(scores), ptr(targets), ptr(lengths), T, ptr(thresholds),
                                   int(bool(end_boundary)), ptr(counts_out)))
+
+
+def winpr_sweep(scores, targets, lengths, thresholds, counts_out, end_boundary=False, k=10):
+    """counts_out int32 [B, T, 3] = {TP, FP, FN} of WinPR(reference=tags, hypothesis=target, k) for every document x threshold
+    (include/mts.h); operands as threshold_sweep; k in 1..64."""
+    B, Lq, n_out, T = _sweep_operands(scores, targets, lengths, thresholds, counts_out, 3)
+    check(lib.mts_winpr_sweep(stream_ptr(), B, Lq, targets.shape[1], n_out, ptr(scores), ptr(targets), ptr(lengths), T, ptr(thresholds),
+                              int(bool(end_boundary)), int(k), ptr(counts_out)))
 
 
 def head_fwd(x, w, b, scores):

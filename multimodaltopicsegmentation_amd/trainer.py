@@ -282,6 +282,11 @@ class NativeTrainer:
         self.apply_optimizer()
         return loss
 
+    def fit(self, train, val=None, **kw):
+        """Epochs over a ResidentCorpus with validation, the learning-rate schedule, early stopping and the best state: fit.fit(self, ...)."""
+        from .fit import fit
+        return fit(self, train, val, **kw)
+
     def _check_same_length(self, Lq):
         """Shards of one global batch are collated together (same padded length).  Ranks that collate separately may differ:
         catch that once per distinct length instead of hanging in mismatched collectives."""
