@@ -162,6 +162,39 @@ int mts_gather_pad(void* stream, int src_dtype, int dst_dtype, int B, int Lmax, 
                    const int32_t* doc_index,    /* device [B], repeats allowed */
                    void* dst,                   /* device [B, Lmax, D] in dst_dtype */
                    float pad_value);
+/* SEGMENT-ORDER GATHER (resident.AugmentedCorpus; reference: the inverse_augmentation of cross_validation_split,
+ * utils/load_datasets_precomputed.py:71-96, done in the gather instead of at load time).  mts_gather_pad with one more table in front of
+ * the source row: destination document b is a list of row ranges of stored document d = doc_index[b], its "listed segments"
+ * j = seg_ptr[b] .. seg_ptr[b + 1] - 1.  Listed segment j holds the destination rows seg_dst[j] <= t < seg_dst[j + 1] (the document's last
+ * one: t < dst_len[b]) and copies them from the document's rows seg_src[j] onwards, both offsets relative to the document's first row:
+ *   dst[b, t, :] = corpus[row_start[d] + seg_src[j] + (t - seg_dst[j]), :]  for t < min(dst_len[b], Lmax), j = the LAST listed segment of b
+ *   with seg_dst[j] <= t;  every other element of dst = pad_value.  seg_dst ascends inside a document and starts at 0.
+ * A row is written as pad, and no source address is formed for it, when doc_index[b] is outside 0 .. n_docs - 1, when no listed segment
+ * holds it (seg_dst of the first one above t, or an empty list), or when its source row falls outside [row_start[d], row_start[d + 1]):
+ * table CONTENTS are ordinary input, MTS_OK whatever they hold (seg_ptr is clamped to 0 .. n_listed); only the table SIZES are trusted, as
+ * row_start is.  Dtypes, rounding, access widths, alignment, 64-bit offsets, "every element of dst written once by a plain vector store,
+ * one launch, no memset, no atomics, no workspace" are those of mts_gather_pad -- the two share their copy units, width selection and copy
+ * loop in csrc/gather.hip.  Rows of 64 or more access units: one wave owns four consecutive destination rows and finds their segment with
+ * scalar loads (a binary search over the document's seg_dst for the first row, a forward walk for the rest); thinner rows: one lane per
+ * destination unit, each lane searching for its own row.
+ * close_last (may be NULL): the LABEL RULE for the targets, D = 1 and F32 -> F32 only (MTS_ERR_INVALID otherwise).  Of the rows copied, the
+ * last row of every listed segment is written as 1.0 whatever the source holds, and the document's last row (t = dst_len[b] - 1, when
+ * it is inside Lmax) as close_last[b] ? 1.0 : 0.0.
+ * MTS_ERR_INVALID before any device work: what mts_gather_pad refuses, n_listed < 0, and with B > 0 a null seg_ptr or dst_len, or with
+ * n_listed > 0 a null seg_dst or seg_src.  B == 0 returns MTS_OK without a launch. */
+int mts_gather_segments(void* stream, int src_dtype, int dst_dtype, int B, int Lmax, int D,
+                        const void* corpus,          /* device [total_rows, D], row-major, contiguous */
+                        const int64_t* row_start,    /* device [n_docs + 1], ascending, row_start[0] = 0 */
+                        int n_docs,
+                        const int32_t* doc_index,    /* device [B], repeats allowed */
+                        const int32_t* seg_ptr,      /* device [B + 1]: listed segments of document b */
+                        const int32_t* seg_dst,      /* device [n_listed]: first destination row, ascending per document */
+                        const int32_t* seg_src,      /* device [n_listed]: first source row inside the stored document */
+                        int n_listed,
+                        const int32_t* dst_len,      /* device [B]: rows of destination document b before the cut at Lmax */
+                        const int32_t* close_last,   /* device [B] or NULL: the label rule */
+                        void* dst,                   /* device [B, Lmax, D] in dst_dtype */
+                        float pad_value);
 
 /* ---------------------------------------------------------------------------------------------
  * LayerNorm family (biased variance, eps inside sqrt).

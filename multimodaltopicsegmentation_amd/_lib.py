@@ -122,6 +122,7 @@ SIGNATURES = {
     'mts_scale': (_i, [_vp, _sz, _vp, _f]),
     'mts_collate_pad': (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _f, _i]),
     'mts_gather_pad': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _f]),
+    'mts_gather_segments': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _f]),
 }
 
 _missing = []

@@ -213,6 +213,27 @@ def gather_pad(corpus, row_start, doc_index, dst, pad_value=0.0):
     return dst
 
 
+def gather_segments(corpus, row_start, doc_index, seg_ptr, seg_dst, seg_src, dst_len, dst, pad_value=0.0, close_last=None):
+    """gather_pad with the documents' segments in a listed order (include/mts.h mts_gather_segments): destination document b is the row
+    ranges j = seg_ptr[b] .. seg_ptr[b + 1] - 1 of stored document doc_index[b], range j landing at destination row seg_dst[j] and read from
+    the document's row seg_src[j] onwards, dst_len[b] rows in all; everything else is pad.  All tables int32 on the device.  close_last
+    (int32 [B], 1-d fp32 corpus only: the targets) applies the label rule: 1 on the last row of every listed segment, close_last[b] on the
+    document's last row.  Every element of dst is written."""
+    B, Lmax = int(dst.shape[0]), int(dst.shape[1])
+    D = 1 if corpus.dim() == 1 else int(corpus.shape[1])
+    assert dst.numel() == B * Lmax * D and dst.is_contiguous() and corpus.is_contiguous()
+    assert row_start.dtype == torch.int64 and row_start.is_contiguous() and row_start.numel() >= 2
+    tables = [doc_index, seg_ptr, seg_dst, seg_src, dst_len] + ([close_last] if close_last is not None else [])
+    assert all(t.dtype == torch.int32 and t.is_contiguous() and t.device == dst.device for t in tables)
+    assert doc_index.numel() == B and seg_ptr.numel() == B + 1 and dst_len.numel() == B and seg_dst.numel() == seg_src.numel()
+    assert close_last is None or close_last.numel() == B
+    assert corpus.device == dst.device == row_start.device
+    check(lib.mts_gather_segments(stream_ptr(), dtype_code(corpus.dtype), dtype_code(dst.dtype), B, Lmax, D, ptr(corpus), ptr(row_start),
+                                  row_start.numel() - 1, ptr(doc_index), ptr(seg_ptr), ptr(seg_dst), ptr(seg_src), seg_dst.numel(),
+                                  ptr(dst_len), ptr(close_last), ptr(dst), float(pad_value)))
+    return dst
+
+
 def embed_layernorm_fwd(x, pos, pos_offset, type0, gamma, beta, eps, y, pre, mean, rstd, row_src=None, x2=None):
     """row_src (int32 [n_rows], optional): packed batch -- output row r is sentence row_src[r] = b*L + i of x.
     x2 (fp32 [B, L, D2], optional): K-split input -- the row is x[b, i] | x2[b, i] and the concatenation is never materialised."""

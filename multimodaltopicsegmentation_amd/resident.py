@@ -16,7 +16,11 @@ at D = 1792, 238 MB in fp32, against 288 GB), so the fastest host collater is no
   * ``DocumentShardSampler(lengths, batch_size, rank, world)`` yields ``(local_indices, pad_to)`` per global batch: the documents
     ``global_batch[rank::world]`` (the rule of ``trainer.shard_batch``) and the longest document of the WHOLE global batch, computed from
     the host length table -- every rank pads to the same length without a collective, so ``NativeTrainer._check_same_length`` passes
-    and no rank collates documents it then throws away.
+    and no rank collates documents it then throws away;
+  * ``corpus.batch_segments(indices, orders, close_last)`` is ``batch()`` with every document's topic segments in a listed order, and
+    ``corpus.augmented('reverse' | 'shuffle')`` an ``AugmentedCorpus``: a view with a reordered twin of every document (segment-order
+    augmentation, the reference's ``inverse_augmentation``) made by the gather itself (``ops.gather_segments``, the same file): the same
+    bytes moved, no second copy of the corpus, a few hundred more integers in the per-call copy.
 
 For every tagger but ``SwitchBiLSTM(switch='dense')`` (see ``trainer.shard_batch``), ``corpus.batch(*item)`` on rank r holds the bits of
 ``shard_batch(collated global batch, r, world)``.  ``NativeTrainer.step`` takes these batches as they are.
@@ -78,6 +82,19 @@ class ResidentCorpus:
         # per-document segment ends, what AudioPortionDataset._segments_of makes from the collated batch: the positions just behind
         # the boundary sentences inside the reported length
         self._segment_ends = [(np.flatnonzero(t.numpy()[:int(n)] == 1) + 1).tolist() for t, n in zip(tgt, self.lengths)] if self.segments else None
+        # the topic segments of the STORED rows (segment-order augmentation): document d's segment j is rows _seg_bounds[d][j] ..
+        # _seg_bounds[d][j + 1]; a segment ends behind a label 1, and what follows the last 1 is the tail
+        self._seg_bounds, self._has_tail, self._binary_labels = [], np.zeros(self.n_docs, dtype=bool), True
+        for k, t in enumerate(tgt):
+            y = t.numpy()
+            ones = y == 1
+            self._binary_labels = self._binary_labels and bool((ones | (y == 0)).all())
+            ends = np.flatnonzero(ones) + 1
+            self._has_tail[k] = bool(rows[k]) and not bool(ones[-1])
+            self._seg_bounds.append(np.concatenate([[0], ends, [rows[k]] if self._has_tail[k] else []]).astype(np.int64))
+        self.n_segments = np.array([b.size - 1 for b in self._seg_bounds], dtype=np.int64)     # segments per document, the tail included
+        self._seg_flat = np.concatenate(self._seg_bounds)                                      # the same bounds, one array: batch_segments
+        self._seg_base = np.concatenate([[0], np.cumsum(self.n_segments + 1)[:-1]]).astype(np.int64)
 
         def upload(docs):
             # fp32 first: the values the reference's `merge` writes into its fp32 batch; bf16 is that batch's .to(torch.bfloat16)
@@ -179,6 +196,202 @@ class ResidentCorpus:
                                                pad_value=0.0 - self.minus)
         return out
 
+    # ---- segment-order augmentation ------------------------------------------------------------------------------------------
+    def _segment_tables(self, ii, orders, close_last):
+        """host tables of batch_segments -> (seg_ptr [B + 1], seg_dst [S], seg_src [S], augmented rows [B], close flags [B]) as int64 /
+        bool arrays.  Built from the segment table made at construction: O(listed segments), never O(rows)."""
+        if not self._binary_labels:
+            raise ValueError('ResidentCorpus: segment orders need targets that are 0 or 1 everywhere (a segment ends behind a 1)')
+        B = int(ii.size)
+        if len(orders) != B:
+            raise ValueError(f'batch_segments: {B} documents but {len(orders)} orders')
+        close = np.asarray(close_last, dtype=bool).reshape(-1)
+        if close.size not in (1, B):
+            raise ValueError(f'batch_segments: close_last is one flag or one per document ({B}), not {close.size}')
+        close = np.broadcast_to(close, (B,))
+        arrs = [np.asarray(o, dtype=np.int64).reshape(-1) for o in orders]
+        counts = np.array([a.size for a in arrs], dtype=np.int64)
+        if not counts.all():
+            d = int(ii[int(np.flatnonzero(counts == 0)[0])])
+            raise ValueError(f'batch_segments: the order of document {d} is empty (a zero-length document is not a batch row)')
+        o = np.concatenate(arrs)
+        doc = np.repeat(ii, counts)                                              # the stored document of every listed segment
+        bad = np.flatnonzero((o < 0) | (o >= self.n_segments[doc]))
+        if bad.size:
+            d = int(doc[bad[0]])
+            raise ValueError(f'batch_segments: document {d} has segments 0 .. {int(self.n_segments[d]) - 1}; its order lists {int(o[bad[0]])}')
+        key = np.repeat(np.arange(B, dtype=np.int64), counts) * (int(self.n_segments.max()) + 1) + o
+        if np.unique(key).size != key.size:
+            raise ValueError('batch_segments: an order lists a segment twice')
+        at = self._seg_base[doc] + o
+        first = self._seg_flat[at]
+        ln = self._seg_flat[at + 1] - first
+        ptr = np.zeros(B + 1, dtype=np.int64)
+        np.cumsum(counts, out=ptr[1:])
+        c = np.cumsum(ln)
+        before = np.concatenate([[0], c[ptr[1:-1] - 1]])                         # rows listed in front of every document
+        return ptr, c - ln - np.repeat(before, counts), first, c[ptr[1:] - 1] - before, close
+
+    def _segment_host_fields(self, ii, tables, pad_to):
+        ptr, dst_off, _, rows, close = tables
+        lengths = np.minimum(rows, self.tv) if self.truncate else rows
+        if self.truncate:
+            if pad_to is not None:
+                raise ValueError('pad_to cannot be combined with truncate=True (every batch is truncate_value long)')
+            Lmax = self.tv
+        else:
+            Lmax = int(rows.max())
+            if pad_to is not None:
+                if int(pad_to) < Lmax:
+                    raise ValueError(f'pad_to {int(pad_to)} is shorter than the longest augmented document ({Lmax})')
+                Lmax = int(pad_to)
+        out = {'id': torch.from_numpy(ii.copy()), 'src_lengths': torch.from_numpy(lengths.astype(np.int64, copy=True)),
+               'domain': [self.domain[i] for i in ii.tolist()] if self.da else None}
+        if self.segments:
+            # the positions just behind the augmented labels' ones, inside the reported length: every listed segment's end but the last
+            # one's, and the document's own end when close_last
+            out['src_segments'] = []
+            for k in range(int(ii.size)):
+                ends = dst_off[ptr[k] + 1:ptr[k + 1]].tolist() + ([int(rows[k])] if close[k] else [])
+                out['src_segments'].append([e for e in ends if e <= int(lengths[k])])
+        return out, Lmax
+
+    def batch_segments(self, indices, orders, close_last, pad_to=None):
+        """``batch()`` with every document's topic segments in a listed order (segment-order augmentation, the reference's
+        ``cross_validation_split(inverse_augmentation=True)``, utils/load_datasets_precomputed.py:71-96, moved into the gather).
+
+        Document d has ``n_segments[d]`` segments: segment j ends behind the j-th label 1, and the rows behind the last 1 are the tail
+        (the loader forces the last label to 0, so loaded documents always have one).  ``orders[k]`` is a non-empty sequence of distinct
+        segment numbers of document ``indices[k]`` -- a subset is fine -- and ``close_last`` one bool, or one per document.  Row k of the
+        batch holds the rows of the listed segments in that order; its labels are 0 except a 1 on the last row of every listed segment,
+        and ``close_last`` on the very last row.  ``src_lengths`` are the augmented lengths (cut at truncate_value by a truncate=True
+        corpus, as a stored document is), ``src_segments`` the positions behind the augmented labels' ones, ``src_tokens2`` is reordered
+        with ``src_tokens``, ``domain`` is the stored document's.  Same keys, dtypes and devices as ``batch()``.
+
+        Everything is validated on the host before a launch: IndexError for an index outside the corpus; ValueError for an empty order,
+        a repeated or unknown segment number, a pad_to below the longest augmented document, and a corpus whose targets are not all 0 / 1.
+        The tables travel with the indices in ONE asynchronous copy out of the pinned ring; the tensors are built by
+        ``ops.gather_segments`` (one launch each, every element written)."""
+        ii = self._indices(indices)
+        if ii.size == 0:
+            return {}
+        tables = self._segment_tables(ii, orders, close_last)
+        out, Lmax = self._segment_host_fields(ii, tables, pad_to)
+        if self.device.type != 'cuda':
+            raise RuntimeError('ResidentCorpus.batch_segments gathers on the GPU (there is no CPU fallback)')
+        from . import ops
+        ptr, dst_off, src_off, rows, close = tables
+        with torch.cuda.device(self.device):
+            B, S = int(ii.size), int(dst_off.size)
+            dev = self._upload_indices(np.concatenate([ii, ptr, rows, close.astype(np.int64), dst_off, src_off]))
+            cut = np.cumsum([B, B + 1, B, B, S, S]).tolist()
+            idx, seg_ptr, dst_len, close_dev, seg_dst, seg_src = (dev[a:b] for a, b in zip([0] + cut[:-1], cut))
+
+            def gather(corpus, dst, **kw):
+                return ops.gather_segments(corpus, self.row_start, idx, seg_ptr, seg_dst, seg_src, dst_len, dst, **kw)
+            out['src_tokens'] = gather(self.corpus, torch.empty((B, Lmax, self.corpus.shape[1]), dtype=self.wire, device=self.device))
+            out['src_tokens2'] = None if self.corpus2 is None else gather(
+                self.corpus2, torch.empty((B, Lmax, self.corpus2.shape[1]), dtype=self.wire, device=self.device))
+            out['tgt_tokens'] = gather(self.targets, torch.empty((B, Lmax), dtype=torch.float32, device=self.device),
+                                       pad_value=0.0 - self.minus, close_last=close_dev)
+        return out
+
+    def augmented(self, mode, seed=0):
+        """-> AugmentedCorpus(self, mode, seed): 2 x n_docs virtual documents, every stored one and its twin with the segments reordered"""
+        return AugmentedCorpus(self, mode, seed=seed)
+
+
+class AugmentedCorpus:
+    """A view of a ResidentCorpus with ``2 * n_docs`` virtual documents: index v < n_docs is stored document v, bit for bit what
+    ``corpus.batch`` gives; index v >= n_docs is the TWIN of document v - n_docs, the same sentences with their topic segments in another
+    order, made in the gather (``ResidentCorpus.batch_segments``).  Nothing is copied: the resident bytes stay what they were.
+
+      * ``mode='reverse'``: the reference's inverse_augmentation (utils/load_datasets_precomputed.py:71-96) -- the closed segments in
+        descending order, the tail (the rows behind the last boundary) left out, the last label 1.  Fixed per document.
+      * ``mode='shuffle'``: ``np.random.default_rng([seed, epoch, d]).permutation(n_segments[d])`` over ALL segments, the tail included,
+        the last label 0: the length stays, and so does the loader's rule that a document ends on a 0.  The same on every rank without
+        a collective and different every epoch (``set_epoch``; the view's sampler sets it).
+
+    Two deviations from the reference, on purpose: (1) a document without a closed segment (no label 1) has an EMPTY reversed twin
+    upstream; here its 'reverse' twin is the unaugmented document (order [0], last label 0), because no kernel of the training step has
+    been shown to take a zero-length document.  (2) The upstream loop stops after the first 11 list entries and runs on into the twins
+    it has just appended; here every document has exactly one twin.
+
+    ``lengths`` (what a batch reports, known without drawing an order), ``host_fields`` (no GPU), ``batch`` and ``sampler`` mirror the
+    corpus'; ``'id'`` holds the virtual indices, ``'domain'`` the stored document's."""
+
+    def __init__(self, corpus, mode, seed=0):
+        if mode not in ('reverse', 'shuffle'):
+            raise ValueError("AugmentedCorpus: mode must be 'reverse' or 'shuffle'")
+        if not corpus._binary_labels:
+            raise ValueError('AugmentedCorpus: the corpus holds targets that are not 0 / 1 (a segment ends behind a 1)')
+        self.corpus, self.mode, self.seed, self.epoch = corpus, mode, int(seed), 0
+        self.n_docs = corpus.n_docs
+        self._closed = corpus.n_segments - corpus._has_tail                         # closed segments per document
+        if mode == 'reverse':
+            twin_rows = np.array([b[c] if c else b[-1] for b, c in zip(corpus._seg_bounds, self._closed)], dtype=np.int64)
+        else:
+            twin_rows = corpus.rows
+        self.rows = np.concatenate([corpus.rows, twin_rows])
+        self.lengths = np.minimum(self.rows, corpus.tv) if corpus.truncate else self.rows.copy()
+
+    def __len__(self):
+        return 2 * self.n_docs
+
+    def set_epoch(self, epoch):
+        """the epoch of the 'shuffle' draws"""
+        self.epoch = int(epoch)
+
+    def order(self, v):
+        """-> (segment order, close_last) of virtual document v"""
+        d = v % self.n_docs
+        K, closed = int(self.corpus.n_segments[d]), int(self._closed[d])
+        if v < self.n_docs:
+            return np.arange(K), closed == K                  # the stored document: every segment in place, its own last label
+        if self.mode == 'shuffle':
+            return np.random.default_rng([self.seed, self.epoch, d]).permutation(K), False
+        if closed == 0:
+            return np.zeros(1, dtype=np.int64), False         # deviation (1)
+        return np.arange(closed - 1, -1, -1), True
+
+    def _virtual(self, indices):
+        vv = np.asarray(indices, dtype=np.int64).reshape(-1)
+        if vv.size and (int(vv.min()) < 0 or int(vv.max()) >= 2 * self.n_docs):
+            raise IndexError(f'AugmentedCorpus: document index outside 0 .. {2 * self.n_docs - 1}')
+        return vv
+
+    def _orders(self, vv):
+        pairs = [self.order(v) for v in vv.tolist()]
+        return [o for o, _ in pairs], [c for _, c in pairs]
+
+    def host_fields(self, indices, pad_to=None):
+        """the host half of ``batch()``: ({'id', 'src_lengths', 'domain'(, 'src_segments')}, padded length); touches no GPU"""
+        vv = self._virtual(indices)
+        if vv.size == 0:
+            return {}, 0
+        if int(vv.max()) < self.n_docs:
+            return self.corpus.host_fields(vv, pad_to)
+        ii = vv % self.n_docs
+        out, Lmax = self.corpus._segment_host_fields(ii, self.corpus._segment_tables(ii, *self._orders(vv)), pad_to)
+        out['id'] = torch.from_numpy(vv.copy())
+        return out, Lmax
+
+    def batch(self, indices, pad_to=None):
+        """the batch dict of virtual documents ``indices``: ``corpus.batch`` when all of them are stored documents, one
+        ``corpus.batch_segments`` call otherwise (a stored document in it goes through with its segments in place)"""
+        vv = self._virtual(indices)
+        if vv.size == 0:
+            return {}
+        if int(vv.max()) < self.n_docs:
+            return self.corpus.batch(vv, pad_to)
+        out = self.corpus.batch_segments(vv % self.n_docs, *self._orders(vv), pad_to=pad_to)
+        out['id'] = torch.from_numpy(vv.copy())
+        return out
+
+    def sampler(self, batch_size, **kw):
+        """a DocumentShardSampler over the virtual documents whose ``set_epoch`` also sets the epoch of this view's 'shuffle' draws"""
+        return _AugmentedSampler(self, 2 * self.n_docs if self.corpus.truncate else self.lengths, batch_size, **kw)
+
 
 class DocumentShardSampler:
     """Rank-local batch sampler for data-parallel training from a ResidentCorpus.
@@ -235,3 +448,16 @@ class DocumentShardSampler:
         for g in self.global_batches():
             pad_to = int(self.lengths[g].max()) if self.lengths is not None else None
             yield g[self.rank::self.world].tolist(), pad_to
+
+
+class _AugmentedSampler(DocumentShardSampler):
+    """AugmentedCorpus.sampler: DocumentShardSampler over the virtual documents; the epoch also reaches the view's 'shuffle' draws"""
+
+    def __init__(self, view, lengths, batch_size, **kw):
+        super().__init__(lengths, batch_size, **kw)
+        self.view = view
+        view.set_epoch(self.epoch)
+
+    def set_epoch(self, epoch):
+        super().set_epoch(epoch)
+        self.view.set_epoch(epoch)

@@ -13,6 +13,14 @@ the report gives each repetition and the spread.
     (iii) ResidentCorpus(wire_dtype='bf16') + DocumentShardSampler: a new batch gathered on the device every step.
 
   python tools/resident_corpus_bench.py [--out profiles/resident_corpus_bench.txt] [--iters 200] [--steps 150] [--reps 3]
+
+--segments runs the legs of segment-order augmentation INSTEAD (DESIGN.md §3 "Segment-order augmentation"; out: profiles/
+segment_augment_bench.txt), same rules:
+(a) mts_gather_pad and mts_gather_segments alone at 64 x 256 x 1792 bf16 out of 256 documents of 256 rows whose segments are about 20 rows
+    long (a 5 % boundary rate): the plain gather, the segment gather with every segment in place, and with the 'shuffle' orders of
+    AugmentedCorpus; a fresh index list and fresh tables per call, uploaded beforehand.  Both kernels move the same bytes.
+(b) NativeTrainer.step of the configs[1] transformer fed by ResidentCorpus + sampler and by AugmentedCorpus('shuffle') + its sampler, and
+    the host half of one augmented batch (drawing the orders, building the tables) timed on its own.
 """
 import argparse
 import json
@@ -152,14 +160,137 @@ def step_legs(steps, warmup, reps, say):
     return {k: [round(t, 4) for t in v] for k, v in ms.items()}
 
 
+def _boundary_lines(g):
+    lines = []
+    for i in range(N_DOCS):
+        y = (torch.rand(L, generator=g) < 0.05).float()
+        y[-1] = 0.0                                                                          # the loader's rule
+        lines.append((torch.randn(L, D, generator=g), y.tolist(), f'doc{i}'))
+    return lines
+
+
+def segment_gather_legs(corpus, iters, reps, say):
+    """(a) of --segments: the three gathers in turn out of one resident corpus"""
+    import numpy as np
+    g = torch.Generator().manual_seed(1)
+    view = corpus.augmented('shuffle', seed=5)
+    lists = torch.randint(0, N_DOCS, (iters + 8, B), generator=g).numpy()
+    dst = torch.empty(B, L, D, dtype=torch.bfloat16, device=DEV)
+
+    def tables(ii, orders):
+        ptr, dst_off, src_off, rows, _ = corpus._segment_tables(ii, orders, False)
+        return [torch.from_numpy(np.ascontiguousarray(t)).to(torch.int32).to(DEV) for t in (ii, ptr, dst_off, src_off, rows)]
+    in_place = [tables(ii, [np.arange(corpus.n_segments[d]) for d in ii]) for ii in lists]
+    shuffled = [tables(ii, [view.order(N_DOCS + int(d))[0] for d in ii]) for ii in lists]
+    # the same documents as ONE range each (no search to speak of): what the table walk in front of the first load costs
+    whole = [[torch.from_numpy(np.ascontiguousarray(t)).to(torch.int32).to(DEV)
+              for t in (ii, np.arange(B + 1), np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.int64), corpus.rows[ii])] for ii in lists]
+    listed = sum(int(t[2].numel()) for t in shuffled) / len(shuffled)
+    # every leg takes ANOTHER index list in the same trip, so that none finds the rows its predecessor has just pulled into the caches
+    legs = {'mts_gather_pad': lambda k: ops.gather_pad(corpus.corpus, corpus.row_start, in_place[k % len(lists)][0], dst),
+            'mts_gather_segments, segments in place': lambda k: ops.gather_segments(corpus.corpus, corpus.row_start, *in_place[(k + 3) % len(lists)], dst),
+            "mts_gather_segments, 'shuffle' orders": lambda k: ops.gather_segments(corpus.corpus, corpus.row_start, *shuffled[(k + 5) % len(lists)], dst),
+            'mts_gather_segments, one listed range per document': lambda k: ops.gather_segments(corpus.corpus, corpus.row_start, *whole[(k + 6) % len(lists)], dst),
+            'mts_gather_pad, once more (last in the trip)': lambda k: ops.gather_pad(corpus.corpus, corpus.row_start, in_place[(k + 7) % len(lists)][0], dst)}
+    nbytes = 2 * B * L * D * 2
+    for k in range(8):                                                                      # warm every leg
+        for f in legs.values():
+            f(k)
+    torch.cuda.synchronize()
+    out = {name: [] for name in legs}
+    for _ in range(reps):
+        ev = {name: [] for name in legs}
+        for k in range(iters):
+            for name, f in legs.items():
+                s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                s.record()
+                f(k)
+                e.record()
+                ev[name].append((s, e))
+        torch.cuda.synchronize()
+        for name in legs:
+            out[name].append(median([s.elapsed_time(e) * 1e3 for s, e in ev[name]]))
+    say(f'(a) one call between two device events, median of {iters} per repetition, the legs in turn; batch {B} x {L} x {D} bf16 -> bf16, '
+        f'{listed / B:.1f} listed segments per document')
+    res = {}
+    for name, us in out.items():
+        rates = [nbytes / (t * 1e-6) / 1e12 for t in us]
+        say(f'  {name:42s} {nbytes / 1e6:7.1f} MB   ' + '  '.join(f'{t:7.1f} us' for t in us) + '   ' + '  '.join(f'{r:5.2f}' for r in rates) + ' TB/s')
+        res[name] = {'MB': round(nbytes / 1e6, 1), 'us': [round(t, 1) for t in us], 'TBps': [round(r, 3) for r in rates]}
+    spread = max(out['mts_gather_pad']) - min(out['mts_gather_pad'])
+    for name in list(legs)[1:]:
+        say(f'  {name} - mts_gather_pad per repetition: ' + '  '.join(f'{a - b:+.1f} us' for a, b in zip(out[name], out['mts_gather_pad']))
+            + f'   (the plain gather\'s own spread: {spread:.1f} us)')
+    return res
+
+
+def segment_step_legs(corpus, steps, warmup, reps, say):
+    """(b) of --segments: the step fed by the corpus and by its augmented view"""
+    def model():
+        return Transformer_segmenter(2, D, 256, num_layers=1, nheads=8, loss_fn='FocalLoss', window_size=30, compute_dtype='bf16', seed=1234).to(DEV)
+    view = corpus.augmented('shuffle', seed=5)
+    sources = {'plain': (corpus, corpus.sampler(B, seed=9)), 'augmented': (view, view.sampler(B, seed=9))}
+    epoch = {name: 0 for name in sources}
+
+    def items(name, n):
+        got = 0
+        sampler = sources[name][1]
+        while got < n:
+            sampler.set_epoch(epoch[name])
+            epoch[name] += 1
+            for item in sampler:
+                if got < n:
+                    got += 1
+                    yield item
+    trainers = {name: NativeTrainer(model(), lr=1e-3, optimizer='Adam') for name in sources}
+    label = {'plain': 'ResidentCorpus(bf16) + sampler', 'augmented': "AugmentedCorpus('shuffle') + its sampler"}
+    ms = {name: [] for name in sources}
+    for _ in range(reps):
+        for name, tr in trainers.items():
+            t0 = None
+            for k, item in enumerate(items(name, warmup + steps)):
+                if k == warmup:
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                tr.step(sources[name][0].batch(*item))
+            torch.cuda.synchronize()
+            ms[name].append(1e3 * (time.perf_counter() - t0) / steps)
+    say(f'(b) NativeTrainer.step, configs[1] transformer bf16 at {B} x {L} x {D}: ms per step over windows of {steps} steps '
+        f'({warmup} warm-up steps each), the legs in turn, {reps} repetitions; corpus {N_DOCS} documents, {corpus.nbytes / 1e6:.0f} MB resident')
+    for name in sources:
+        say(f'  {label[name]:48s} ' + '  '.join(f'{t:.4f}' for t in ms[name]) + f'   median {median(ms[name]):.4f}  spread {max(ms[name]) - min(ms[name]):.4f}')
+    say('  augmented - plain per repetition: ' + '  '.join(f'{1e3 * (a - b):+.1f} us' for a, b in zip(ms['augmented'], ms['plain'])))
+    # the host half of a batch on its own (no GPU work): what the loop's host thread pays per step before it can launch anything
+    host = {}
+    for name, (src, _) in sources.items():
+        todo = list(items(name, steps))
+        t0 = time.perf_counter()
+        for item in todo:
+            src.host_fields(*item)
+        host[name] = 1e6 * (time.perf_counter() - t0) / steps
+    view.set_epoch(0)
+    t0 = time.perf_counter()
+    for d in range(N_DOCS):
+        view.order(N_DOCS + d)
+    draw = 1e6 * (time.perf_counter() - t0) / N_DOCS
+    say(f'  host half of one batch (host_fields, no launch): plain {host["plain"]:.0f} us, augmented {host["augmented"]:.0f} us; '
+        f'one \'shuffle\' draw (np.random.default_rng([seed, epoch, d]).permutation(K)) {draw:.1f} us, about {B // 2} per batch')
+    return {'step_ms': {k: [round(t, 4) for t in v] for k, v in ms.items()}, 'host_us': {k: round(v, 1) for k, v in host.items()},
+            'draw_us': round(draw, 1)}
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'resident_corpus_bench.txt'))
+    ap.add_argument('--out', default=None)
+    ap.add_argument('--segments', action='store_true', help='the legs of segment-order augmentation instead (module docstring)')
     ap.add_argument('--iters', type=int, default=200)
     ap.add_argument('--steps', type=int, default=150)
     ap.add_argument('--warmup', type=int, default=15)
     ap.add_argument('--reps', type=int, default=3)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles',
+                             'segment_augment_bench.txt' if a.segments else 'resident_corpus_bench.txt')
     if not torch.cuda.is_available():
         sys.exit('resident_corpus_bench: no GPU visible; nothing is measured without one')
     lines = []
@@ -167,9 +298,16 @@ def main():
     def say(s):
         print(s, flush=True)
         lines.append(s)
-    say(f'tools/resident_corpus_bench.py --iters {a.iters} --steps {a.steps} --warmup {a.warmup} --reps {a.reps}   ({torch.cuda.get_device_name(0)})')
-    res = {'gather': gather_legs(a.iters, a.reps, say)}
-    res['step_ms'] = step_legs(a.steps, a.warmup, a.reps, say)
+    say(f'tools/resident_corpus_bench.py {"--segments " if a.segments else ""}--iters {a.iters} --steps {a.steps} --warmup {a.warmup} --reps {a.reps}'
+        f'   ({torch.cuda.get_device_name(0)})')
+    if a.segments:
+        ds = AudioPortionDataset(_boundary_lines(torch.Generator().manual_seed(4321)), {'0': 0, '1': 1}, CRF=False, truncate=False)
+        corpus = ResidentCorpus(ds, DEV, wire_dtype='bf16')
+        res = {'gather': segment_gather_legs(corpus, a.iters, a.reps, say)}
+        res.update(segment_step_legs(corpus, a.steps, a.warmup, a.reps, say))
+    else:
+        res = {'gather': gather_legs(a.iters, a.reps, say)}
+        res['step_ms'] = step_legs(a.steps, a.warmup, a.reps, say)
     say(json.dumps(res))
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, 'w') as f:
