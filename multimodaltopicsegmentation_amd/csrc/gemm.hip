@@ -936,7 +936,8 @@ extern "C" int mts_gemm(void* stream, int a_dtype, int c_dtype, int layout, int 
     else if (layout == MTS_TT) { s.sam = 1; s.sak = lda; s.sbn = ldb; s.sbk = 1; }
     else { s.sam = 1; s.sak = lda; s.sbn = 1; s.sbk = ldb; }
     MTS_CHECK_ARG(ldc % 4 == 0 && ((uintptr_t)C % 16) == 0, "mts_gemm(f32): C must be 16-byte aligned with ldc %% 4 == 0");
-    MTS_CHECK_ARG(!(epilogue & MTS_EPI_RESIDUAL) || (ldr % 4 == 0), "mts_gemm(f32): ldr %% 4");
+    MTS_CHECK_ARG(!(epilogue & MTS_EPI_RESIDUAL) || (ldr % 4 == 0 && ((uintptr_t)residual % 16) == 0), "mts_gemm(f32): residual must be 16-byte aligned with ldr %% 4 == 0");
+    MTS_CHECK_ARG(!aux || (ldaux % 4 == 0 && ((uintptr_t)aux % 16) == 0), "mts_gemm(f32): aux must be 16-byte aligned with ldaux %% 4 == 0");   // epilogue4 stores it as float4
     // "gemm_f32_mfma" = 1 (default): exact-fp32 matrix-core kernel; 0: the VALU kernel (A/B, and the form the round-1 fixtures ran on)
     // split-K for the weight-gradient shapes (K = all tokens, a handful of 128 x 128 output tiles: dW_hh of one LSTM direction is 16
     // tiles on 256 CUs): up to 16 slices of >= 512 k each while the launch stays within one wave of workgroups; plain or
@@ -979,6 +980,9 @@ extern "C" int mts_gemm(void* stream, int a_dtype, int c_dtype, int layout, int 
   const size_t ws_planes = workspace_bytes > MTS_GEMM_WS_HEAD ? workspace_bytes - MTS_GEMM_WS_HEAD : 0;
   float* const planes = workspace ? (float*)((char*)workspace + MTS_GEMM_WS_HEAD) : nullptr;
   plan_bf16(c_dtype, layout, M, N, K, epilogue, workspace != nullptr && ws_planes > 0, ws_planes, &use256, &splits);
+  // store_tile_256 / store_tile_224 write bf16 C as 16-byte pieces whenever N % 8 == 0 and ldc % 8 == 0, without looking at the base; the check
+  // above admits an 8-byte aligned C.  Such a C goes to the 128x128 kernel, whose vec_ok gate tests the base and falls back to 8-byte stores.
+  if (use256 && c_dtype != MTS_F32 && ((uintptr_t)C % 16) != 0) use256 = 0;
   g_last_tile = use256 == 2 ? 224 : use256 == 1 ? 256 : 128;
   g_last_splits = splits;
   a.slab = nullptr;

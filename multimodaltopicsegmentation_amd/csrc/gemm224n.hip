@@ -299,7 +299,8 @@ bool mts_gemm224n_applies(const GemmArgs& a, int layout, bool c_is_f32, int spli
          (a.ldc % 8 == 0) && (((uintptr_t)a.C & 15) == 0) && (a.lda % 8 == 0) && (a.ldb % 8 == 0) && (((uintptr_t)a.A & 15) == 0) &&
          (((uintptr_t)a.B & 15) == 0) && spanB < 0x7ff00000u && (size_t)256 * a.lda * 2 + (size_t)a.K * 2 < 0x7ff00000u &&
          (!(a.epi & MTS_EPI_COLSCALE) || a.ncols_scaled % 4 == 0) &&
-         (!(a.epi & MTS_EPI_RESIDUAL) || (a.ldr % 4 == 0 && ((uintptr_t)a.residual & 7) == 0)) &&
+         // (the residual tile is copied to the LDS in 16-byte pieces)
+         (!(a.epi & MTS_EPI_RESIDUAL) || (a.ldr % 8 == 0 && ((uintptr_t)a.residual & 15) == 0)) &&
          (!(a.epi & MTS_EPI_BIAS) || ((uintptr_t)a.bias & 15) == 0);
 }
 

@@ -256,7 +256,8 @@ int mts_launch_gemm224r(const GemmArgs& a, int layout, bool c_is_f32, int splits
   const bool ok = !a.slab && (a.epi & ~simple) == 0 && (a.M % 256 == 0) && (a.N % R_BN == 0) && (a.K % BK == 0) && a.K % (2 * BK) == 0 && a.K >= 4 * BK && a.ksplit == a.K &&
                   (a.ldc % 8 == 0) && (((uintptr_t)a.C & 15) == 0) && (a.lda % 8 == 0) && (a.ldb % 8 == 0) &&
                   (!(a.epi & MTS_EPI_COLSCALE) || a.ncols_scaled % 4 == 0) &&
-                  (!(a.epi & MTS_EPI_RESIDUAL) || (a.ldr % 4 == 0 && ((uintptr_t)a.residual & 7) == 0)) &&
+                  // (the residual tile is copied to the LDS in 16-byte pieces: res_copy)
+                  (!(a.epi & MTS_EPI_RESIDUAL) || (a.ldr % 8 == 0 && ((uintptr_t)a.residual & 15) == 0)) &&
                   (!(a.epi & MTS_EPI_BIAS) || ((uintptr_t)a.bias & 15) == 0);
   if (!ok) return -1;
   return d_launch(a, st);
