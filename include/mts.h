@@ -428,6 +428,24 @@ int mts_pair_score_bwd(void* stream, int dtype, int B, int L, int H, const void*
                        const float* dscores, void* dF, int lddf, void* dG, int lddg);
 
 /* ---------------------------------------------------------------------------------------------
+ * Gated merge of two encoder outputs: BiLSTMLateFusion(merge='gate').  An extension: the reference concatenates (models/CRF.py:425, :469)
+ * and has no gate, so DESIGN.md "Gated late-fusion merge" is the specification.
+ * a, h1, h2, m, dm, da, dh1, dh2: [rows, W] act dtype with leading dimensions in ELEMENTS; a = the gate's pre-activation.
+ * forward:  z = sigmoid(a) = 1 / (1 + expf(-a));  m = z h1 + (1 - z) h2  (= h2 + z (h1 - h2)).
+ * backward: dh1 = dm z;  dh2 = dm - dm z;  da = dm (h1 - h2) z (1 - z);  z is recomputed from a.  The caller adds da W_g to dh1 / dh2.
+ * fp32 arithmetic, every output rounded once and OVERWRITTEN; outputs may not overlap the inputs or each other.  Saturation is exact:
+ * a = +-1e4 gives z = 1 | 0, m = h1 | h2 bit for bit and da = 0; a finite input never gives a NaN or an Inf.
+ * Streaming: 16-byte accesses when W, every leading dimension and every base allow (fp32: always; bf16: multiples of 8 elements and
+ * 16-byte bases), 4-element accesses otherwise; no atomics, no workspace, no LDS, one launch, 64-bit offsets; bitwise reproducible.
+ * MTS_ERR_INVALID before any device work: unknown dtype; W < 1; W or a leading dimension no multiple of 4; a leading dimension below
+ * W; a base not aligned to a 4-element vector (16 bytes in fp32, 8 in bf16); with rows > 0 a null operand.  rows == 0: MTS_OK, no launch.
+ * ------------------------------------------------------------------------------------------- */
+int mts_gate_merge_fwd(void* stream, int dtype, size_t rows, int W, const void* a, int lda, const void* h1, int ldh1, const void* h2,
+                       int ldh2, void* m, int ldm);
+int mts_gate_merge_bwd(void* stream, int dtype, size_t rows, int W, const void* a, int lda, const void* h1, int ldh1, const void* h2,
+                       int ldh2, const void* dm, int lddm, void* da, int ldda, void* dh1, int lddh1, void* dh2, int lddh2);
+
+/* ---------------------------------------------------------------------------------------------
  * Cosine auxiliary segment loss.  Replaces cosine_loss / aggregate_embeddings + nn.CosineEmbeddingLoss() of the `segments=` branch of
  * BiLSTM.loss and BiLSTMLateFusion.loss (models/CRF.py:23-92, :322-337, :427-442).
  * x, dx: [B*L, W] act dtype with leading dimensions in ELEMENTS (late fusion hands in a view).  int32 device tables, built on the host

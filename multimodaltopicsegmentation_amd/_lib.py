@@ -90,6 +90,8 @@ SIGNATURES = {
     'mts_rmsnorm_bwd': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'mts_pair_score_fwd': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
     'mts_pair_score_bwd': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i]),
+    'mts_gate_merge_fwd': (_i, [_vp, _i, _sz, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i]),
+    'mts_gate_merge_bwd': (_i, [_vp, _i, _sz, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i]),
     'mts_segment_cosine_workspace': (_sz, [_i, _i, _i]),
     'mts_segment_cosine_fwd': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     'mts_segment_cosine_bwd': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _f, _i, _vp, _i, _vp]),

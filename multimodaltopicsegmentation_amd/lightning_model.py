@@ -52,9 +52,15 @@ class TextSegmenter(_Base):
                  architecture='biLSTMCRF', lr=0.01, dropout_in=0.0, dropout_out=0.0, optimizer='SGD', positional_encoding=True,
                  nheads=8, end_boundary=False, threshold=None, search_threshold=False, metric='Pk', cosine_loss=False,
                  zero_baseline=False, loss_fn='CrossEntropy', no_validation=False, all_results=False, all_scores=False, alpha=0.9,
-                 gamma=2, attention_window=120, switch='dense', compute_dtype=None, ksplit=False, restricted=True):
+                 gamma=2, attention_window=120, switch='dense', compute_dtype=None, ksplit=False, restricted=True, fusion_merge='concat'):
         super().__init__()
         self.validation = not no_validation
+        # fusion_merge (extension, default 'concat'): 'gate' makes architecture='BiLSTMLateFusion' merge its two encoders through a learned
+        # sigmoid gate instead of concatenating them (BiLSTMLateFusion(merge='gate')); no other architecture has two encoders to merge
+        if fusion_merge not in BiLSTMLateFusion.MERGES:
+            raise ValueError(f'fusion_merge must be one of {BiLSTMLateFusion.MERGES}, got {fusion_merge!r}')
+        if fusion_merge != 'concat' and architecture != 'BiLSTMLateFusion':
+            raise ValueError(f"fusion_merge='{fusion_merge}' applies to architecture='BiLSTMLateFusion' only, not to '{architecture}'")
         # ksplit=True (extension, default off): an early-fusion model takes the batch's two embedding tensors ('src_tokens' = text,
         # 'src_tokens2' = audio, as AudioPortionDataset(second_input=...) collates them) as ONE input of width D1 + D2 without the
         # host-side concat of utils/load_datasets_precomputed.py:158-161 ever being made (datasets.load_dataset_from_precomputed(
@@ -88,7 +94,8 @@ class TextSegmenter(_Base):
         elif architecture == 'BiLSTMLateFusion':
             self.model = BiLSTMLateFusion(tagset_size, embedding_dim, hidden_dim, num_layers=num_layers, bidirectional=bidirectional,
                                           dropout_in=dropout_in, dropout_out=dropout_out, batch_first=batch_first, LSTM=LSTM,
-                                          loss_fn=loss_fn, threshold=threshold, alpha=alpha, gamma=gamma, compute_dtype=compute_dtype)
+                                          loss_fn=loss_fn, threshold=threshold, alpha=alpha, gamma=gamma, compute_dtype=compute_dtype,
+                                          merge=fusion_merge)
             self.double_input = True
         elif architecture == 'SheikhBiLSTM':
             # lightning_model.py:245-247: dropout_in 0.5 (live in eval mode too), dropout_attention 0 and batch_first are hard-wired;

@@ -424,6 +424,24 @@ def pair_score_bwd(F, G, dscores, B, Lq, dF, dG):
                                      ptr(dF), dF.stride(0), ptr(dG), dG.stride(0)))
 
 
+def gate_merge_fwd(a, h1, h2, m):
+    """m = z h1 + (1 - z) h2 with z = sigmoid(a) (include/mts.h "Gated merge").  a, h1, h2, m: [rows, W] views in the activation dtype
+    (row strides free, columns contiguous); m is overwritten."""
+    rows, W = a.shape
+    with _timed(('gate_fwd', rows, W)):
+        check(lib.mts_gate_merge_fwd(stream_ptr(), dtype_code(a.dtype), rows, W, ptr(a), a.stride(0), ptr(h1), h1.stride(0), ptr(h2), h2.stride(0),
+                                     ptr(m), m.stride(0)))
+    return m
+
+
+def gate_merge_bwd(a, h1, h2, dm, da, dh1, dh2):
+    """Backward of gate_merge_fwd: da = dm (h1 - h2) z (1 - z), dh1 = dm z, dh2 = dm - dm z, all three overwritten (z recomputed from a)."""
+    rows, W = a.shape
+    with _timed(('gate_bwd', rows, W)):
+        check(lib.mts_gate_merge_bwd(stream_ptr(), dtype_code(a.dtype), rows, W, ptr(a), a.stride(0), ptr(h1), h1.stride(0), ptr(h2), h2.stride(0),
+                                     ptr(dm), dm.stride(0), ptr(da), da.stride(0), ptr(dh1), dh1.stride(0), ptr(dh2), dh2.stride(0)))
+
+
 class SegmentTable:
     """Host tables of the cosine auxiliary segment loss (include/mts.h "Cosine auxiliary segment loss"), int32 numpy arrays:
     seg [n_seg, 8], pair [n_pair, 4], row_map [B * L]."""

@@ -413,7 +413,13 @@ class BiLSTM(_RnnTaggerBase):
 
 
 class BiLSTMLateFusion(_RnnTaggerBase):
-    """models/CRF.py:371-479: two independent RNNs, plain concat (there is no gate in the reference), one head."""
+    """models/CRF.py:371-479: two independent RNNs, plain concat (there is no gate in the reference), one head.
+
+    merge='gate' (extension, default 'concat'; DESIGN.md "Gated late-fusion merge"): the head reads m = z h1 + (1 - z) h2 with
+    z = sigmoid([h1 ; h2] W_g^T + b_g), a learned per-unit choice between the two encoders, instead of [h1 ; h2].  Adds the parameters
+    ``gate.weight`` [2H, 4H] and ``gate.bias`` [2H]; ``classification.weight`` is then [n_out, 2H].  Everything around the merge (loss,
+    un-padding, decode, threshold, ``segments=``) is the concat mode's."""
+    MERGES = ('concat', 'gate')
     takes_segments = True            # as BiLSTM
     concurrent_encoders = True       # model1 / model2 on two HIP streams (bitwise the same results).  Under a data-parallel hook too:
                                      # model2's spans are announced from inside `with stream(side)`, so the collective is issued
@@ -426,8 +432,11 @@ class BiLSTMLateFusion(_RnnTaggerBase):
 
     def __init__(self, tagset_size, embedding_dim, hidden_dim, num_layers=1, bidirectional=True, dropout_in=0.0, dropout_out=0.0,
                  batch_first=True, LSTM=True, loss_fn='CrossEntropy', threshold=None, device=None, alpha=0.9, gamma=2,
-                 compute_dtype=None, seed=None):
+                 compute_dtype=None, seed=None, merge='concat'):
         super().__init__()
+        if merge not in self.MERGES:
+            raise ValueError(f"merge must be one of {self.MERGES}, got {merge!r}")
+        self.merge = merge
         self._init_common(loss_fn, threshold, alpha, gamma, compute_dtype)
         self._check_rnn_args(dropout_in, dropout_out, LSTM, bidirectional)
         self.embedding_dim, self.hidden_dim, self.tagset_size, self.num_layers = embedding_dim, hidden_dim, tagset_size, num_layers
@@ -435,13 +444,23 @@ class BiLSTMLateFusion(_RnnTaggerBase):
         gen = torch.Generator().manual_seed(torch.initial_seed() if seed is None else seed)
         g1, i1, p1 = _rnn_groups('model1.', embedding_dim[0], hidden_dim, num_layers, gen)
         g2, i2, p2 = _rnn_groups('model2.', embedding_dim[1], hidden_dim, num_layers, gen)
-        self._hp = round_up(hidden_dim, 8)
-        cw, cb = _linear_init(self.n_out, 4 * hidden_dim, gen)
-        groups = g1 + g2 + [[('classification.weight', (self.n_out, 4 * self._hp)), ('classification.bias', (self.n_out,))]]
+        H, Hp = hidden_dim, round_up(hidden_dim, 8)
+        self._hp = Hp
+        nblocks = 2 if merge == 'gate' else 4             # hidden vectors the head reads: the merged one | the concatenation
+        cw, cb = _linear_init(self.n_out, nblocks * H, gen)
+        groups = g1 + g2 + [[('classification.weight', (self.n_out, nblocks * Hp)), ('classification.bias', (self.n_out,))]]
         init = {**i1, **i2, 'classification.weight': cw, 'classification.bias': cb}
         pads = {**p1, **p2}
-        if _head_pad(hidden_dim, 4):
-            pads['classification.weight'] = _head_pad(hidden_dim, 4)
+        if _head_pad(H, nblocks):
+            pads['classification.weight'] = _head_pad(H, nblocks)
+        if merge == 'gate':
+            # drawn after the head's: a given seed leaves both encoders' initial weights as they are in concat mode.  Zero bias and a small
+            # weight: z starts near 1/2, the merge near the mean of the two encoders
+            init['gate.weight'], init['gate.bias'] = _linear_init(2 * H, 4 * H, gen)[0], torch.zeros(2 * H)
+            groups.append([('gate.weight', (2 * Hp, 4 * Hp)), ('gate.bias', (2 * Hp,))])
+            if Hp != H:                                    # padded units are inert: h = 0 there, so m, da and every pad gradient are exactly 0
+                pads['gate.weight'] = [(0, 2, H, Hp), (1, 4, H, Hp)]
+                pads['gate.bias'] = [(0, 2, H, Hp)]
         self._init_flat(FlatLayout(groups, pads), init)
         self._rnn1 = _RnnStack(self, 'model1.', embedding_dim[0], hidden_dim, num_layers, 'r1')
         self._rnn2 = _RnnStack(self, 'model2.', embedding_dim[1], hidden_dim, num_layers, 'r2')
@@ -466,6 +485,8 @@ class BiLSTMLateFusion(_RnnTaggerBase):
             h2, s2 = self._rnn2.forward(self._drop_in(self._to_act(xb), 'r2'), li32, B, Lq)
         h1, m1 = self._drop_out(h1, 'r1')
         h2, m2 = self._drop_out(h2, 'r2')
+        if self.merge == 'gate':
+            return self._fwd_gate(B, Lq, li32, h1, h2, s1, s2, m1, m2)
         cat = self._ws.get('cat', B * Lq, 4 * H, self.compute_dtype, x1.device)
         cat[:, :2 * H].copy_(h1)                       # torch.cat((x1, x2), axis=2), models/CRF.py:425
         cat[:, 2 * H:].copy_(h2)
@@ -473,8 +494,43 @@ class BiLSTMLateFusion(_RnnTaggerBase):
         ops.head_fwd(cat, self._w(self._flat, 'classification.weight'), self._w(self._flat, 'classification.bias'), scores)
         return dict(B=B, L=Lq, li32=li32, cat=cat, s1=s1, s2=s2, m1=m1, m2=m2, scores=scores.view(B, Lq, self.n_out))
 
+    def _fwd_gate(self, B, Lq, li32, h1, h2, s1, s2, m1, m2):
+        """The gated merge and the head on it (both encoders joined on the issuing stream).  a = h1 W_g[:, :2H]^T + h2 W_g[:, 2H:]^T + b_g as
+        two GEMMs on the column halves of W_g: no concatenated buffer exists in this mode.  The second product reaches the first call as
+        its residual operand, from a buffer of its own (the bias + residual epilogue of every NT kernel is what the suite tests)."""
+        N, W, dt, dev = B * Lq, 2 * self._hp, self.compute_dtype, h1.device
+        wg = self._w(self._weights(), 'gate.weight')
+        a2 = self._ws.get('gate_a2', N, W, dt, dev)
+        ops.linear_fwd(h2, wg[:, W:], None, a2)
+        a = self._ws.get('gate_a', N, W, dt, dev)
+        ops.linear_fwd(h1, wg[:, :W], self._w(self._flat, 'gate.bias'), a, residual=a2)
+        m = self._ws.get('gate_m', N, W, dt, dev)
+        ops.gate_merge_fwd(a, h1, h2, m)
+        scores = self._ws.get('scores', N, self.n_out, torch.float32, dev)
+        ops.head_fwd(m, self._w(self._flat, 'classification.weight'), self._w(self._flat, 'classification.bias'), scores)
+        return dict(B=B, L=Lq, li32=li32, cat=m, a=a, h1=h1, h2=h2, s1=s1, s2=s2, m1=m1, m2=m2, scores=scores.view(B, Lq, self.n_out))
+
+    def _bwd_gate(self, st, dm, d1, d2):
+        """dm -> d1, d2 (the two encoders' output gradients) and the gate's parameter gradients, announced before the encoders start."""
+        N, W, dt, dev = dm.shape[0], 2 * self._hp, self.compute_dtype, dm.device
+        g, lay = self.grad_flat(), self._layout
+        da = self._ws.get('gate_da', N, W, dt, dev)
+        p1 = self._ws.get('gate_p1', N, W, dt, dev)
+        p2 = self._ws.get('gate_p2', N, W, dt, dev)
+        ops.gate_merge_bwd(st['a'], st['h1'], st['h2'], dm, da, p1, p2)
+        dwg = lay.view(g, 'gate.weight')
+        ops.colsum(da, lay.view(g, 'gate.bias'))
+        ops.linear_wgrad(da, st['h1'], dwg[:, :W])
+        ops.linear_wgrad(da, st['h2'], dwg[:, W:])
+        self._grads_ready(*self._span_of('gate.weight', 'gate.bias'))
+        # d1 = dm z + da W_g[:, :2H]: the kernel's part comes in as the residual operand (act-dtype NN output + residual: tested for every kernel)
+        wg = self._w(self._weights(), 'gate.weight')
+        ops.linear_dgrad(da, wg[:, :W], d1, residual=p1)
+        ops.linear_dgrad(da, wg[:, W:], d2, residual=p2)
+
     def loss_and_grad(self, x1, x2, lengths, tags, want_grad=True, segments=None):
-        """segments: as BiLSTM.loss_and_grad (models/CRF.py:427-442); the cosine loss reads the concatenation of the two encoders' outputs."""
+        """segments: as BiLSTM.loss_and_grad (models/CRF.py:427-442); the cosine loss reads the concatenation of the two encoders' outputs
+        (merge='gate': the merged output)."""
         L.require_gpu()
         tab = self._segment_tables(segments, x1, lengths, tags) if segments is not None else None
         st = self._fwd(x1, x2, lengths)
@@ -489,13 +545,19 @@ class BiLSTMLateFusion(_RnnTaggerBase):
             g, lay = self.grad_flat(), self._layout
             ops.head_bwd_params(st['cat'], dsc, lay.view(g, 'classification.weight'), lay.view(g, 'classification.bias'))
             self._grads_ready(*self._span_of('classification.weight', 'classification.bias'))
-            dcat = self._ws.get('dcat', B * Lq, 4 * H, self.compute_dtype, dev)
-            ops.head_bwd_data(dsc, self._w(self._flat, 'classification.weight'), dcat)
-            self._cosine_bwd(tab, cos_ws, dcat)
             d1 = self._ws.get('dout1', B * Lq, 2 * H, self.compute_dtype, dev)
             d2 = self._ws.get('dout2', B * Lq, 2 * H, self.compute_dtype, dev)
-            d1.copy_(dcat[:, :2 * H])
-            d2.copy_(dcat[:, 2 * H:])
+            if self.merge == 'gate':
+                dm = self._ws.get('gate_dm', B * Lq, 2 * H, self.compute_dtype, dev)
+                ops.head_bwd_data(dsc, self._w(self._flat, 'classification.weight'), dm)
+                self._cosine_bwd(tab, cos_ws, dm)
+                self._bwd_gate(st, dm, d1, d2)
+            else:
+                dcat = self._ws.get('dcat', B * Lq, 4 * H, self.compute_dtype, dev)
+                ops.head_bwd_data(dsc, self._w(self._flat, 'classification.weight'), dcat)
+                self._cosine_bwd(tab, cos_ws, dcat)
+                d1.copy_(dcat[:, :2 * H])
+                d2.copy_(dcat[:, 2 * H:])
             if st['m1'] is not None:
                 ops.dropout_bwd(d1, d1, st['m1'], self.dropout_out)
                 ops.dropout_bwd(d2, d2, st['m2'], self.dropout_out)
