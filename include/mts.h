@@ -606,6 +606,22 @@ int mts_crf_nll(void* stream, int B, int L, int C, const float* feats, const flo
  * index (torch.max).  C == 4 keeps its back-pointers in LDS up to L = 10 240 and uses bp_ws (the generic kernel) beyond. */
 int mts_crf_viterbi(void* stream, int B, int L, int C, const float* feats, const int32_t* lengths,
                     const float* trans, float* best_score, int32_t* paths, int32_t* bp_ws);
+/* Posterior (max-marginal) decode, an extension (the reference decodes by Viterbi only; DESIGN.md "CRF posterior-marginal decode"):
+ * the forward-backward recursion of models/CRF.py:218-240 without tags.  With alpha_0 the START one-hot (-1e4 convention),
+ * alpha_{t+1}(i) = lse_j(alpha_t(j) + T[i][j]) + f_t(i), beta_n(i) = T[stop][i], beta_t(j) = lse_i(T[i][j] + f_t(i) + beta_{t+1}(i)),
+ * lm_t(i) = alpha_{t+1}(i) + beta_{t+1}(i) - log Z:
+ *   scores[b, t] = clamp(lm_t(cls) - lse_{i != cls} lm_t(i), -80, +80) for t < n_b, exactly 0 for t >= n_b  (fp32 [B, L], every element
+ *   written); logz[b] = lse_i(alpha_n(i) + T[stop][i]) (fp32 [B], may be NULL; n_b = 0 included).
+ * A logit for the 1-wide decode rule sigmoid(score) > th (mts_greedy_decode, the threshold sweeps): sigmoid(+80) is exactly 1 in fp32 and
+ * sigmoid(-80) a normal positive number, so no threshold in (0, 1) decodes the clamped score differently.  C in 3..8, cls in 0..C-1;
+ * lengths may be NULL and are clamped to 0..L.  No atomics; bitwise reproducible from launch to launch.
+ * Numeric domain of C == 4: as mts_crf_nll -- that path carries softmax(alpha) in fp32 (the scaled recursion), so a step's worst
+ * filtered-probability ratio exp(-(2 Se + 2 St)) -- Se, St: the largest |emission| and |finite transition| -- must stay a normal fp32:
+ * emission spread plus transition spread below about 87 nats per step.  Inside it the scores are finite and within tolerance
+ * (tests/test_gpu_crf_marginal.py at +-30 / +-10); beyond it a tag's probability underflows to 0 and a score can be wrong (still finite:
+ * the clamp drops a NaN) WITHOUT an error code.  The generic path (C != 4) works in the log domain and has no such limit. */
+int mts_crf_marginals(void* stream, int B, int L, int C, int cls, const float* feats, const int32_t* lengths,
+                      const float* trans, float* scores, float* logz, float* workspace /* mts_crf_workspace(B, L, C) bytes */);
 
 /* ---------------------------------------------------------------------------------------------
  * Optimizer step over a flat fp32 parameter buffer.

@@ -376,3 +376,138 @@ extern "C" int mts_crf_viterbi(void* stream, int B, int L, int C, const float* f
   MTS_LAUNCH_CHECK("mts_crf_viterbi");
   return MTS_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// Posterior (max-marginal) decode: scores[b, t] = log P(y_t = cls | x) - log P(y_t != cls | x), a logit the 1-wide decode rule of
+// loss_elems.h (sigmoid(score) > th) reads unchanged.  The forward-backward sweeps of the NLL kernels above without tags, gold path, 1/B
+// and transition gradient; the logit is formed from the per-tag marginals themselves (never from 1 - p: a small probability keeps its
+// relative precision) and clamped to +-80, where sigmoid_f is exactly 1 / a normal positive fp32, so no threshold in (0, 1) decodes the
+// clamped score differently.  DESIGN.md "CRF posterior-marginal decode".
+// ------------------------------------------------------------------------------------------------
+#define CRF_LOGIT_CLAMP 80.f
+
+// C == 4: the scaled recursion of crf_nll4_kernel (its forward step, arithmetic for arithmetic; same numeric domain).  The STOP row is
+// shifted by its largest entry among the tags that carry probability, so a document of length 0 gives log Z = T[stop][start] exactly.
+__global__ __launch_bounds__(64) void crf_marg4_kernel(int B, int L, int cls, const float* __restrict__ feats, const int32_t* __restrict__ lengths,
+                                                       const float* __restrict__ trans, float* __restrict__ scores, float* __restrict__ logz,
+                                                       float* __restrict__ alphas) {
+  constexpr int C = 4, start = 2, stop = 3;
+  const int i = threadIdx.x & 3;
+  const int b = blockIdx.x * 16 + (threadIdx.x >> 2);
+  if (b >= B) return;                                   // whole quads leave together
+  const int n = lengths ? max(min(lengths[b], L), 0) : L;
+  float Er[4], Ec[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { Er[j] = expf(trans[i * C + j]); Ec[j] = expf(trans[j * C + i]); }
+  const float tstop = trans[stop * C + i];
+  const float* f = feats + (size_t)b * L * C;
+  float* al = alphas + (size_t)b * (L + 1) * C;
+  float* sc = scores + (size_t)b * L;
+  float p = (i == start) ? 1.f : 0.f;
+  al[i] = p;
+  float logscale = 0.f;
+  float fq[4];
+#pragma unroll
+  for (int d = 0; d < 4; ++d) fq[d] = d < n ? f[d * C + i] : 0.f;
+  for (int t = 0; t < n; ++t) {
+    const float ft = fq[0];
+    fq[0] = fq[1]; fq[1] = fq[2]; fq[2] = fq[3];
+    fq[3] = (t + 4 < n) ? f[(t + 4) * C + i] : 0.f;
+    const float sgm = ((Er[0] * quad_bcast<0>(p) + Er[1] * quad_bcast<1>(p)) + Er[2] * quad_bcast<2>(p)) + Er[3] * quad_bcast<3>(p);
+    const float m = quad_max(sgm > 0.f ? ft : -INFINITY);
+    const float e = sgm > 0.f ? expf(ft - m) : 0.f;
+    const float u = sgm * e;
+    const float z = quad_sum(u);
+    p = u / z;
+    logscale += logf(z) + m;
+    al[(t + 1) * C + i] = p;
+  }
+  const float ms = quad_max(p > 0.f ? tstop : -INFINITY);
+  const float es = p > 0.f ? expf(tstop - ms) : 0.f;
+  const float zn = quad_sum(p * es);
+  if (logz && i == 0) logz[b] = logscale + (ms + logf(zn));
+  // reverse sweep: scaled beta recursion; P(y_t = i) = p_{t+1}(i) bhat_{t+1}(i)
+  float bh = es / zn;                                    // bhat_n(i)
+  float f0 = n > 0 ? f[(n - 1) * C + i] : 0.f, f1 = n > 1 ? f[(n - 2) * C + i] : 0.f;
+  float a0 = n > 0 ? al[(n - 1) * C + i] : 0.f, a1 = n > 1 ? al[(n - 2) * C + i] : 0.f;
+  float pnext = p;
+  for (int t = n - 1; t >= 0; --t) {
+    const float ft = f0, pt = a0;
+    f0 = f1; a0 = a1;
+    if (t >= 2) { f1 = f[(t - 2) * C + i]; a1 = al[(t - 2) * C + i]; }
+    const float sgm = ((Er[0] * quad_bcast<0>(pt) + Er[1] * quad_bcast<1>(pt)) + Er[2] * quad_bcast<2>(pt)) + Er[3] * quad_bcast<3>(pt);
+    const float m = quad_max(sgm > 0.f ? ft : -INFINITY);       // (the forward step's own arithmetic: the same z, bit for bit)
+    const float e = sgm > 0.f ? expf(ft - m) : 0.f;
+    const float z = quad_sum(sgm * e);
+    const float marg = pnext * bh;
+    const float m0 = quad_bcast<0>(marg), m1 = quad_bcast<1>(marg), m2 = quad_bcast<2>(marg), m3 = quad_bcast<3>(marg);
+    const float mine = cls == 0 ? m0 : cls == 1 ? m1 : cls == 2 ? m2 : m3;
+    const float rest = ((cls == 0 ? 0.f : m0) + (cls == 1 ? 0.f : m1)) + ((cls == 2 ? 0.f : m2) + (cls == 3 ? 0.f : m3));
+    // log 0 - log 0 (both marginals lost: outside the numeric domain) is a NaN, which fmaxf drops: the score stays finite
+    if (i == 0) sc[t] = fminf(fmaxf(logf(mine) - logf(rest), -CRF_LOGIT_CLAMP), CRF_LOGIT_CLAMP);
+    const float w = e * bh / z;                          // e_t(i) bhat_{t+1}(i) / z_t
+    bh = fminf(((Ec[0] * quad_bcast<0>(w) + Ec[1] * quad_bcast<1>(w)) + Ec[2] * quad_bcast<2>(w)) + Ec[3] * quad_bcast<3>(w), 1e30f);
+    pnext = pt;
+  }
+  for (int t = n + i; t < L; t += 4) sc[t] = 0.f;
+}
+
+// generic C (3..8): one thread per document in the log domain, as crf_nll_kernel.  The logit is a difference of alpha + beta sums of one
+// step, so the rounding alpha and beta have in common cancels without a normalisation by log Z.
+__global__ __launch_bounds__(64) void crf_marg_kernel(int B, int L, int C, int cls, const float* __restrict__ feats, const int32_t* __restrict__ lengths,
+                                                      const float* __restrict__ trans, float* __restrict__ scores, float* __restrict__ logz,
+                                                      float* __restrict__ alphas /*[B][L+1][C]*/) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= B) return;
+  const int start = C - 2, stop = C - 1;
+  const int n = lengths ? max(min(lengths[b], L), 0) : L;
+  float T[CRF_MAXC][CRF_MAXC];
+  for (int i = 0; i < C; ++i)
+    for (int j = 0; j < C; ++j) T[i][j] = trans[i * C + j];
+  const float* f = feats + (size_t)b * L * C;
+  float* al = alphas + (size_t)b * (L + 1) * C;
+  float* sc = scores + (size_t)b * L;
+  float a[CRF_MAXC], tmp[CRF_MAXC];
+  for (int i = 0; i < C; ++i) { a[i] = (i == start) ? 0.f : CRF_IMPOSSIBLE; al[i] = a[i]; }
+  for (int t = 0; t < n; ++t) {
+    float nw[CRF_MAXC];
+    for (int i = 0; i < C; ++i) {
+      for (int j = 0; j < C; ++j) tmp[j] = a[j] + T[i][j] + f[t * C + i];
+      nw[i] = lse_arr(tmp, C);
+    }
+    for (int i = 0; i < C; ++i) { a[i] = nw[i]; al[(t + 1) * C + i] = nw[i]; }
+  }
+  for (int i = 0; i < C; ++i) tmp[i] = a[i] + T[stop][i];
+  if (logz) logz[b] = lse_arr(tmp, C);
+  float beta[CRF_MAXC];
+  for (int i = 0; i < C; ++i) beta[i] = T[stop][i];
+  for (int t = n - 1; t >= 0; --t) {
+    float rest[CRF_MAXC], nb[CRF_MAXC];
+    float mine = 0.f;
+    int k = 0;
+    for (int i = 0; i < C; ++i) {
+      const float v = al[(t + 1) * C + i] + beta[i];             // log P(y_t = i) + log Z
+      if (i == cls) mine = v;
+      else rest[k++] = v;
+    }
+    sc[t] = fminf(fmaxf(mine - lse_arr(rest, C - 1), -CRF_LOGIT_CLAMP), CRF_LOGIT_CLAMP);
+    for (int j = 0; j < C; ++j) {
+      for (int i = 0; i < C; ++i) tmp[i] = T[i][j] + f[t * C + i] + beta[i];
+      nb[j] = lse_arr(tmp, C);
+    }
+    for (int i = 0; i < C; ++i) beta[i] = nb[i];
+  }
+  for (int t = n; t < L; ++t) sc[t] = 0.f;
+}
+
+extern "C" int mts_crf_marginals(void* stream, int B, int L, int C, int cls, const float* feats, const int32_t* lengths, const float* trans,
+                                 float* scores, float* logz, float* workspace) {
+  MTS_CHECK_ARG(B > 0 && L > 0 && C >= 3 && C <= CRF_MAXC, "mts_crf_marginals: bad shape (C must be in 3..8)");
+  MTS_CHECK_ARG(cls >= 0 && cls < C, "mts_crf_marginals: cls must be in 0..C-1");
+  MTS_CHECK_ARG(feats && trans && scores && workspace, "mts_crf_marginals: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  if (C == 4) hipLaunchKernelGGL(crf_marg4_kernel, dim3(ceil_div(B, 16)), dim3(64), 0, st, B, L, cls, feats, lengths, trans, scores, logz, workspace);
+  else hipLaunchKernelGGL(crf_marg_kernel, dim3(ceil_div(B, 64)), dim3(64), 0, st, B, L, C, cls, feats, lengths, trans, scores, logz, workspace);
+  MTS_LAUNCH_CHECK("mts_crf_marginals");
+  return MTS_OK;
+}

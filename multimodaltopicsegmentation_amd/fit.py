@@ -69,7 +69,7 @@ def monitor_mode(search_threshold, metric):
 
 def _refusal(model, metric):
     """Why a threshold cannot be searched for this model and metric (TextSegmenter._sweep_refusal's reasons), or None."""
-    if isinstance(model, BiRnnCrf):
+    if isinstance(model, BiRnnCrf) and model.decode == 'viterbi':
         return "search_threshold: architecture 'biLSTMCRF' decodes by Viterbi and has no decision threshold to search"
     if str(metric).lower() == 'b':
         return (f"search_threshold: metric '{metric}' (B-measure) needs the third-party package segeval and is not in the threshold-sweep "

@@ -52,9 +52,16 @@ class TextSegmenter(_Base):
                  architecture='biLSTMCRF', lr=0.01, dropout_in=0.0, dropout_out=0.0, optimizer='SGD', positional_encoding=True,
                  nheads=8, end_boundary=False, threshold=None, search_threshold=False, metric='Pk', cosine_loss=False,
                  zero_baseline=False, loss_fn='CrossEntropy', no_validation=False, all_results=False, all_scores=False, alpha=0.9,
-                 gamma=2, attention_window=120, switch='dense', compute_dtype=None, ksplit=False, restricted=True, fusion_merge='concat'):
+                 gamma=2, attention_window=120, switch='dense', compute_dtype=None, ksplit=False, restricted=True, fusion_merge='concat',
+                 crf_decode='viterbi'):
         super().__init__()
         self.validation = not no_validation
+        # crf_decode (extension, default 'viterbi'): 'marginal' makes architecture='biLSTMCRF' score every sentence with the logit of its
+        # posterior marginal and decode by prob > th (BiRnnCrf(decode='marginal')), so threshold, search_threshold and all_scores apply to it
+        if crf_decode not in BiRnnCrf.DECODES:
+            raise ValueError(f'crf_decode must be one of {BiRnnCrf.DECODES}, got {crf_decode!r}')
+        if crf_decode != 'viterbi' and architecture != 'biLSTMCRF':
+            raise ValueError(f"crf_decode='{crf_decode}' applies to architecture='biLSTMCRF' only, not to '{architecture}'")
         # fusion_merge (extension, default 'concat'): 'gate' makes architecture='BiLSTMLateFusion' merge its two encoders through a learned
         # sigmoid gate instead of concatenating them (BiLSTMLateFusion(merge='gate')); no other architecture has two encoders to merge
         if fusion_merge not in BiLSTMLateFusion.MERGES:
@@ -76,7 +83,7 @@ class TextSegmenter(_Base):
             self.cos = False
             self.model = BiRnnCrf(tagset_size, embedding_dim, hidden_dim, num_layers=num_layers, bidirectional=bidirectional,
                                   dropout_in=dropout_in, dropout_out=dropout_out, batch_first=batch_first, LSTM=LSTM,
-                                  architecture='rnn', compute_dtype=compute_dtype)
+                                  architecture='rnn', compute_dtype=compute_dtype, decode=crf_decode)
         elif architecture == 'BiLSTM':
             self.model = BiLSTM(tagset_size, embedding_dim, hidden_dim, num_layers=num_layers, bidirectional=bidirectional,
                                 dropout_in=dropout_in, dropout_out=dropout_out, batch_first=batch_first, LSTM=LSTM, loss_fn=loss_fn,
@@ -200,7 +207,7 @@ class TextSegmenter(_Base):
 
     def _sweep_refusal(self):
         """Why the threshold sweep does not apply to this model, or None."""
-        if isinstance(self.model, BiRnnCrf):
+        if isinstance(self.model, BiRnnCrf) and self.model.decode == 'viterbi':
             return "search_threshold: architecture 'biLSTMCRF' decodes by Viterbi and has no decision threshold to search"
         if self.metric.lower() in ('b', 'scaiano'):
             return f"search_threshold: metric '{self.metric}' (B-measure / WinPR) is not in the threshold-sweep kernel; use 'Pk', 'WD' or 'F1'"

@@ -744,6 +744,13 @@ def crf_viterbi(feats, lengths, trans, best_score, paths):
     check(lib.mts_crf_viterbi(stream_ptr(), B, Lq, C, ptr(feats), ptr(lengths), ptr(trans), ptr(best_score), ptr(paths), ptr(ws)))
 
 
+def crf_marginals(feats, lengths, trans, scores, cls=1, logz=None):
+    """scores fp32 [B, L] (every element OVERWRITTEN): the clamped logit of P(y_t = cls | x), 0 past a document's length; logz fp32 [B]."""
+    B, Lq, C = feats.shape
+    ws = _scratch(lib.mts_crf_workspace(B, Lq, C), feats.device, 'crf')
+    check(lib.mts_crf_marginals(stream_ptr(), B, Lq, C, int(cls), ptr(feats), ptr(lengths), ptr(trans), ptr(scores), ptr(logz), ptr(ws)))
+
+
 def adam_step(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, grad_scale=1.0, bf16_copy=None):
     check(lib.mts_adam_step(stream_ptr(), param.numel(), ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), lr, beta1, beta2,
                             eps, step, grad_scale, ptr(bf16_copy)))

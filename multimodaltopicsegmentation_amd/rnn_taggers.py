@@ -592,11 +592,23 @@ class BiLSTMLateFusion(_RnnTaggerBase):
 
 
 class BiRnnCrf(_RnnTaggerBase):
-    """models/CRF.py:243-272 composed with CRF (:98-240): RNN -> fc(2H -> tags+2) -> CRF NLL / Viterbi."""
+    """models/CRF.py:243-272 composed with CRF (:98-240): RNN -> fc(2H -> tags+2) -> CRF NLL / Viterbi.
+
+    decode='marginal' (extension, default 'viterbi'; DESIGN.md "CRF posterior-marginal decode"): ``forward`` scores every sentence with the
+    logit of its posterior marginal P(y_t = 1 | x) (mts_crf_marginals) and decodes by ``sigmoid(score) > th`` like the other taggers, so the
+    threshold sweeps apply.  It needs tagset_size == 2 (class 1 must be a real tag).  ``decode`` is not state: the parameters, the loss and
+    the state_dict are those of the default model."""
+    DECODES = ('viterbi', 'marginal')
+    _GUARDED_ENTRY_POINTS = _TaggerBase._GUARDED_ENTRY_POINTS + ('marginal_scores',)
 
     def __init__(self, tagset_size, embedding_dim, hidden_dim, num_layers=1, bidirectional=True, dropout_in=0.0, dropout_out=0.0,
-                 batch_first=True, LSTM=True, architecture='rnn', compute_dtype=None, seed=None):
+                 batch_first=True, LSTM=True, architecture='rnn', compute_dtype=None, seed=None, decode='viterbi'):
         super().__init__()
+        if decode not in self.DECODES:
+            raise ValueError(f'decode must be one of {self.DECODES}, got {decode!r}')
+        if decode == 'marginal' and tagset_size != 2:
+            raise ValueError(f"decode='marginal' needs tagset_size == 2 (class 1 must be a real tag), got {tagset_size}")
+        self.decode = decode
         self._init_common('CrossEntropy', None, 0.9, 2, compute_dtype)
         self._check_rnn_args(dropout_in, dropout_out, LSTM, bidirectional)
         self.embedding_dim, self.hidden_dim, self.tagset_size, self.num_layers = embedding_dim, hidden_dim, tagset_size, num_layers
@@ -659,9 +671,28 @@ class BiRnnCrf(_RnnTaggerBase):
             return self._autograd_loss(lambda: self.loss_and_grad(xs, lengths, tags, True)[0])
         return self.loss_and_grad(xs, lengths, tags, False)[0].clone()
 
-    def forward(self, xs, lenghts):
-        """models/CRF.py:267-272 -> (best_score [B], best_paths list of int lists)."""
+    def _marginal_scores(self, st):
+        B, Lq = st['B'], st['L']
+        scores = torch.empty(B, Lq, 1, dtype=torch.float32, device=st['feats'].device)
+        ops.crf_marginals(st['feats'], st['li32'], self._w(self._flat, 'crf.transitions'), scores.view(B, Lq), cls=1)
+        return scores
+
+    def marginal_scores(self, xs, lengths):
+        """-> [B, Lq, 1] fp32: the logit of P(y_t = 1 | x) clamped to +-80, 0 past a document's length (either decode mode)."""
         L.require_gpu()
+        with torch.no_grad():
+            return self._marginal_scores(self._fwd(xs, lengths))
+
+    def forward(self, xs, lenghts, threshold=0.4):
+        """models/CRF.py:267-272 -> (best_score [B], best_paths list of int lists).  decode='marginal': (scores [B, Lq, 1], list of
+        per-document bool lists) by sigmoid(score) > th, ``.th`` over the argument, as BiLSTM.forward."""
+        L.require_gpu()
+        if self.decode == 'marginal':
+            with torch.no_grad():
+                st = self._fwd(xs, lenghts)
+                scores = self._marginal_scores(st)
+                tags = self._decode(scores, st['li32'], lenghts, threshold)
+            return scores, tags
         with torch.no_grad():
             st = self._fwd(xs, lenghts)
             B, Lq = st['B'], st['L']

@@ -9,7 +9,9 @@ EQUALS what ``test_step`` reports at that threshold over the same documents.
 
 Deviations from upstream's dead code, all on purpose: the probability is the decode rule's (upstream compares the raw ``tag[:, 1]``
 with the threshold, which is wrong for 1-wide heads); F1 sees the operands as ``test_step`` leaves them (target's last sentence 0).
-Not covered: metric 'b' (B-measure: boundary edit distance lives in segeval), the CRF tagger (Viterbi decode has no threshold).
+Not covered: metric 'b' (B-measure: boundary edit distance lives in segeval), the CRF tagger in its default Viterbi decode (a best path
+has no threshold).  Covered since the posterior-marginal decode: ``BiRnnCrf(decode='marginal')`` / ``TextSegmenter(crf_decode='marginal')``
+scores every sentence with the logit of P(y_t = 1 | x) (mts_crf_marginals), a 1-wide head like any other to this sweep.
 
 WinPR (``metric='scaiano'``): ``add`` launches ``mts_winpr_sweep`` instead, three integers ``{TP, FP, FN}`` per document x threshold of
 upstream's call ``WinPR(reference=tags, hypothesis=target)`` (lightning_model.py:622) on the operands the scaiano branch of ``test_step``
