@@ -521,6 +521,17 @@ int mts_threshold_sweep(void* stream, int B, int L, int Lt, int n_out, const flo
  * MTS_ERR_INVALID additionally for k outside 1..64. */
 int mts_winpr_sweep(void* stream, int B, int L, int Lt, int n_out, const float* scores, const float* targets,
                     const int32_t* lengths, int T, const float* thresholds, int end_boundary, int k, int32_t* counts_out);
+/* BOOTSTRAP RESAMPLING SUMS.  Replaces the host loop of train_fit.py:540-562 / compute_accuracy_metrics_sentence.py:63-260 (10 000 x
+ * DataFrame.sample(frac=1, replace=True) and a mean per metric).  values: DEVICE float64 [M, n], M metric rows over n documents;
+ * sums: DEVICE float64 [M, S], every element written.  Resample s (0 .. S-1) draws n indices with replacement by the counter hash of
+ * the dropout kernels (splitmix64 finaliser of seed + 0x9E3779B97F4A7C15 * (idx + 1), upper 32 bits), no RNG state:
+ *   i_j        = (uint32)(((uint64)hash32(seed, (uint64)s * n + j) * (uint64)n) >> 32),   j = 0 .. n-1
+ *   sums[m, s] = ((0 + values[m, i_0]) + values[m, i_1]) + ... + values[m, i_{n-1}]       float64, added in that order
+ * All M rows share the draw (a resampled document keeps its metrics paired).  The multiply-shift draw gives every index floor(2^32 / n)
+ * or one more of the 2^32 hash values: a relative bias below n / 2^32.  The division by n is the caller's.  Bitwise reproducible: a host
+ * loop with the same hash gives the same bits.  One launch, no workspace, no atomics.
+ * MTS_ERR_INVALID before any device work for n outside 1..2^20, M outside 1..16, S outside 1..2^22, null operands. */
+int mts_bootstrap_sums(void* stream, int n, int M, int S, const double* values, uint64_t seed, double* sums);
 /* scores[r, c] = x[r,:] . w[c,:] + b[c]  (x act dtype [rows, D]; w fp32 [n_out, D]); n_out in 1..4 */
 int mts_head_fwd(void* stream, int dtype, int rows, int D, int n_out, const void* x, int ldx, const float* w,
                  const float* b, float* scores);

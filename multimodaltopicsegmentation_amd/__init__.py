@@ -14,7 +14,8 @@ from .t5_taggers import RecurrentLongT5  # noqa: F401
 from .taggers import RestrictedTransformerEncoderLayer, Transformer_segmenter  # noqa: F401
 from .threshold_search import DEFAULT_THRESHOLDS, ThresholdSweep  # noqa: F401
 from .fit import fit  # noqa: F401
+from .evaluate import bootstrap_ci, cross_validate, evaluate, paired_bootstrap  # noqa: F401
 
 __all__ = ['TextSegmenter', 'Transformer_segmenter', 'BiLSTM', 'BiLSTMLateFusion', 'BiRnnCrf', 'RecurrentLongT5', 'SheikhBiLSTM', 'SwitchBiLSTM', 'AudioPortionDataset',
            'AudioPortionDatasetInference', 'RestrictedTransformerEncoderLayer', 'DevicePrefetcher', 'ThresholdSweep', 'DEFAULT_THRESHOLDS', 'ResidentCorpus',
-           'DocumentShardSampler', 'AugmentedCorpus', 'fit']
+           'DocumentShardSampler', 'AugmentedCorpus', 'fit', 'evaluate', 'bootstrap_ci', 'paired_bootstrap', 'cross_validate']

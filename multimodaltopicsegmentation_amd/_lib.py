@@ -100,6 +100,7 @@ SIGNATURES = {
     'mts_greedy_decode': (_i, [_vp, _i, _i, _i, _vp, _vp, _f, _vp]),
     'mts_threshold_sweep': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp]),
     'mts_winpr_sweep': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _vp]),
+    'mts_bootstrap_sums': (_i, [_vp, _i, _i, _i, _vp, C.c_uint64, _vp]),
     'mts_head_fwd': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     'mts_head_bwd_params': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     'mts_head_bwd_data': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i]),

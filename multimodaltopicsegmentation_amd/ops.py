@@ -604,6 +604,22 @@ def winpr_sweep(scores, targets, lengths, thresholds, counts_out, end_boundary=F
                               int(bool(end_boundary)), int(k), ptr(counts_out)))
 
 
+def bootstrap_sums(values, samples, seed=0, out=None):
+    """-> float64 [M, samples] on the device: sums[m, s] = the sequential float64 sum of values[m, i_0 .. i_{n-1}], the n indices of
+    resample s drawn with replacement by the counter hash of (seed, s * n + j) and shared by the M rows (include/mts.h).  values: float64
+    [M, n] (or [n]) on the device; n 1..2^20, M 1..16, samples 1..2^22.  One launch."""
+    if values.dim() == 1:
+        values = values.view(1, -1)
+    assert values.dim() == 2 and values.dtype == torch.float64 and values.is_contiguous() and values.device.type == 'cuda'
+    M, n = values.shape
+    S = int(samples)
+    if out is None:
+        out = torch.empty(M, max(S, 0), dtype=torch.float64, device=values.device)
+    assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() == M * max(S, 0) and out.device == values.device
+    check(lib.mts_bootstrap_sums(stream_ptr(), n, M, S, ptr(values), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(out)))
+    return out
+
+
 def head_fwd(x, w, b, scores):
     rows, D = x.shape
     check(lib.mts_head_fwd(stream_ptr(), dtype_code(x.dtype), rows, D, w.shape[0], ptr(x), x.stride(0), ptr(w), ptr(b), ptr(scores)))

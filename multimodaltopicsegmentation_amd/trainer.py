@@ -287,6 +287,11 @@ class NativeTrainer:
         from .fit import fit
         return fit(self, train, val, **kw)
 
+    def evaluate(self, corpus, **kw):
+        """The test pass over a ResidentCorpus: per-document Pk / WD / F1 / WinPR, their means and the integers: evaluate.evaluate(self, ...)."""
+        from .evaluate import evaluate
+        return evaluate(self, corpus, **kw)
+
     def _check_same_length(self, Lq):
         """Shards of one global batch are collated together (same padded length).  Ranks that collate separately may differ:
         catch that once per distinct length instead of hanging in mismatched collectives."""
