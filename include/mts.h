@@ -195,6 +195,50 @@ int mts_gather_segments(void* stream, int src_dtype, int dst_dtype, int B, int L
                         const int32_t* close_last,   /* device [B] or NULL: the label rule */
                         void* dst,                   /* device [B, Lmax, D] in dst_dtype */
                         float pad_value);
+/* NEGATIVE-SENTENCE MASKING (resident.MaskedCorpus; reference: --mask_inner_sentences / --mask_probability,
+ * utils/load_datasets_precomputed.py:174-185, done per batch on the device instead of once at load time): the PLAN of a masked batch.
+ * For batch row b, d = doc_index[b], rows r = 0 .. n-1 of document d (n = row_start[d + 1] - row_start[d], below 2^31):
+ *   row r is KEPT when targets[row_start[d] + r] != 0, or when (uint64) mts_hash32(doc_seed[b], r) < T,
+ *   T = clamp((uint64)(keep_probability * 4294967296.0), 0, 2^32), computed in double; mts_hash32 is the counter hash of the dropout
+ *   kernels (splitmix64's finaliser of doc_seed + 0x9E3779B97F4A7C15 * (r + 1), high 32 bits).  keep_probability is the chance that a
+ *   NEGATIVE row stays (upstream's code: `rand() > mask_probability and not label` drops): 1.0 keeps every row, 0.0 drops every negative,
+ *   a boundary row is never dropped.  If no row of a non-empty document is kept, row 0 is kept (upstream would make an empty document).
+ *   kept[b]       = the number of kept rows, NOT clipped to Lmax;
+ *   src_row[b, t] = the document-relative index of the t-th kept row for t < min(kept[b], Lmax), -1 behind it.
+ * A doc_index outside 0 .. n_docs - 1, or a document without rows, gives kept[b] = 0 and a row of -1; no address is formed from such an
+ * index.  Every element of src_row and kept is written exactly once by a plain vector store: no memset in front, no atomics, no
+ * workspace; integers, so bitwise reproducible.  One workgroup per batch row walks the document in chunks (any length): keep flags from
+ * the hash, the place inside a wave from the popcount of the wave's ballot below the lane, the waves' totals through LDS, the running
+ * count in a register.  mts_gather_rows builds the batch from src_row.
+ * MTS_ERR_INVALID before any device work: B < 0, Lmax < 1, n_docs < 1, keep_probability outside [0, 1] or NaN, and with B > 0 a null
+ * pointer.  B == 0 returns MTS_OK without a launch. */
+int mts_mask_plan(void* stream, int B, int Lmax,
+                  const float* targets,        /* device [total_rows] */
+                  const int64_t* row_start,    /* device [n_docs + 1], ascending, row_start[0] = 0 */
+                  int n_docs,
+                  const int32_t* doc_index,    /* device [B], repeats allowed */
+                  const uint64_t* doc_seed,    /* device [B] */
+                  double keep_probability,
+                  int32_t* src_row,            /* device [B, Lmax] out */
+                  int32_t* kept);              /* device [B] out */
+/* ROW-TABLE GATHER: mts_gather_pad with a row table in front of the source row.
+ *   dst[b, t, :] = corpus[row_start[d] + src_row[b, t], :]  when 0 <= src_row[b, t] < row_start[d + 1] - row_start[d],  d = doc_index[b];
+ *   every other element of dst = pad_value.
+ * A negative entry, one at or behind the document's end, and every row of a doc_index outside 0 .. n_docs - 1 is written as pad without
+ * forming an address: table CONTENTS are ordinary input, as in mts_gather_segments.  Dtypes, rounding, access widths, alignment, 64-bit
+ * offsets, "every element of dst written once by a plain vector store, one launch, no memset, no atomics, no workspace" and the refusals
+ * are those of mts_gather_pad -- the three gathers share their copy units, width selection and copy loop in csrc/gather.hip.  Rows of
+ * 64 or more access units: one wave owns four consecutive destination rows and reads their table entries as wave-uniform values;
+ * thinner rows (the targets, D = 1, which travel with their rows: no label rule): one lane per destination unit.
+ * MTS_ERR_INVALID before any device work: what mts_gather_pad refuses, and with B > 0 a null src_row.  B == 0 returns MTS_OK. */
+int mts_gather_rows(void* stream, int src_dtype, int dst_dtype, int B, int Lmax, int D,
+                    const void* corpus,          /* device [total_rows, D], row-major, contiguous */
+                    const int64_t* row_start,    /* device [n_docs + 1], ascending, row_start[0] = 0 */
+                    int n_docs,
+                    const int32_t* doc_index,    /* device [B], repeats allowed */
+                    const int32_t* src_row,      /* device [B, Lmax]: document-relative source row of every destination row */
+                    void* dst,                   /* device [B, Lmax, D] in dst_dtype */
+                    float pad_value);
 
 /* ---------------------------------------------------------------------------------------------
  * LayerNorm family (biased variance, eps inside sqrt).

@@ -8,7 +8,7 @@ from .encoder_dataset import AudioPortionDataset, AudioPortionDatasetInference  
 from .datasets import load_dataset_for_inference, load_dataset_from_precomputed, second_input_of  # noqa: F401
 from .lightning_model import TextSegmenter  # noqa: F401
 from .prefetch import DevicePrefetcher  # noqa: F401
-from .resident import AugmentedCorpus, DocumentShardSampler, ResidentCorpus  # noqa: F401
+from .resident import AugmentedCorpus, DocumentShardSampler, MaskedCorpus, ResidentCorpus  # noqa: F401
 from .rnn_taggers import BiLSTM, BiLSTMLateFusion, BiRnnCrf, SheikhBiLSTM, SwitchBiLSTM  # noqa: F401
 from .t5_taggers import RecurrentLongT5  # noqa: F401
 from .taggers import RestrictedTransformerEncoderLayer, Transformer_segmenter  # noqa: F401
@@ -18,4 +18,4 @@ from .evaluate import bootstrap_ci, cross_validate, evaluate, paired_bootstrap  
 
 __all__ = ['TextSegmenter', 'Transformer_segmenter', 'BiLSTM', 'BiLSTMLateFusion', 'BiRnnCrf', 'RecurrentLongT5', 'SheikhBiLSTM', 'SwitchBiLSTM', 'AudioPortionDataset',
            'AudioPortionDatasetInference', 'RestrictedTransformerEncoderLayer', 'DevicePrefetcher', 'ThresholdSweep', 'DEFAULT_THRESHOLDS', 'ResidentCorpus',
-           'DocumentShardSampler', 'AugmentedCorpus', 'fit', 'evaluate', 'bootstrap_ci', 'paired_bootstrap', 'cross_validate']
+           'DocumentShardSampler', 'AugmentedCorpus', 'MaskedCorpus', 'fit', 'evaluate', 'bootstrap_ci', 'paired_bootstrap', 'cross_validate']

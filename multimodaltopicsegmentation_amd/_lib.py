@@ -127,6 +127,8 @@ SIGNATURES = {
     'mts_collate_pad': (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _f, _i]),
     'mts_gather_pad': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _f]),
     'mts_gather_segments': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _f]),
+    'mts_mask_plan': (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, C.c_double, _vp, _vp]),
+    'mts_gather_rows': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _f]),
 }
 
 _missing = []

@@ -13,8 +13,9 @@
 //
 // mts_gather_segments is the same stream with one more table in front of the source row: a document is gathered as a list of its own
 // row ranges ("listed segments": a destination offset and a source offset each), which reorders its topic segments on the way into the
-// batch (resident.AugmentedCorpus).  Both entry points share the units (CopyOp / CastOp), the width selection (with_units) and the
-// copy loop (copy_rows) below, so that they cannot drift apart; only the rule that names a destination row's source row differs.
+// batch (resident.AugmentedCorpus).  mts_gather_rows names every destination row's source row in a table of its own (resident.MaskedCorpus:
+// the table is the plan mts_mask_plan made).  The three entry points share the units (CopyOp / CastOp), the width selection (gather) and
+// the copy loop (copy_rows) below, so that they cannot drift apart; only the rule that names a destination row's source row differs.
 #include <algorithm>
 #include <type_traits>
 #include "common.h"
@@ -273,7 +274,70 @@ __global__ __launch_bounds__(256) void gather_seg_thin_kernel(const typename Op:
   dst[idx] = v;
 }
 
+// ---- mts_gather_rows ------------------------------------------------------------------------------------------------------------
+// The third rule: a row table in front of the source row (negative-sentence masking: mts_mask_plan writes the table, mask_plan.hip).
+// Destination row (b, i) copies the document's row src_row[b, i]; a negative entry, one at or behind the document's end, or an index
+// outside the corpus is a pad row, and no address is formed from it.  In the wave-per-row kernel b and i are wave-uniform, so the entry
+// is one scalar load.
+__device__ __forceinline__ int64_t table_row(int b, int i, int Lmax, const int64_t* __restrict__ row_start, int n_docs,
+                                             const int32_t* __restrict__ doc_index, const int32_t* __restrict__ src_row) {
+  const int d = doc_index[b];
+  if ((unsigned)d >= (unsigned)n_docs) return -1;
+  const int64_t s = row_start[d];
+  const int64_t e = src_row[(int64_t)b * Lmax + i];
+  return e >= 0 && e < row_start[d + 1] - s ? s + e : -1;
+}
+
+template <typename Op>
+__global__ __launch_bounds__(WAVES_PER_BLOCK* MTS_WAVE) void gather_tab_rows_kernel(const typename Op::S* __restrict__ corpus,
+                                                                                    const int64_t* __restrict__ row_start, int n_docs,
+                                                                                    const int32_t* __restrict__ doc_index,
+                                                                                    const int32_t* __restrict__ src_row,
+                                                                                    typename Op::T* __restrict__ dst, int64_t rows, int Lmax,
+                                                                                    int U, uint4 pad16) {
+  typedef typename Op::S S;
+  typedef typename Op::T T;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int lane = threadIdx.x & (MTS_WAVE - 1);
+  const int64_t r0 = ((int64_t)blockIdx.x * WAVES_PER_BLOCK + wave) * ROWS_PER_WAVE;
+  if (r0 >= rows) return;
+  const T padv = pad_as(pad16, (T*)nullptr);
+  int b = (int)(r0 / Lmax), i = (int)(r0 - (int64_t)b * Lmax);
+  const S* src[ROWS_PER_WAVE];
+  bool live[ROWS_PER_WAVE];
+#pragma unroll
+  for (int k = 0; k < ROWS_PER_WAVE; ++k) {
+    live[k] = r0 + k < rows;
+    src[k] = nullptr;
+    if (live[k]) {
+      const int64_t s = table_row(b, i, Lmax, row_start, n_docs, doc_index, src_row);
+      if (s >= 0) src[k] = corpus + s * U;
+    }
+    if (++i == Lmax) { i = 0; ++b; }
+  }
+  copy_rows<Op>(src, live, dst + r0 * U, U, lane, padv);
+}
+
+template <typename Op>
+__global__ __launch_bounds__(256) void gather_tab_thin_kernel(const typename Op::S* __restrict__ corpus, const int64_t* __restrict__ row_start,
+                                                              int n_docs, const int32_t* __restrict__ doc_index,
+                                                              const int32_t* __restrict__ src_row, typename Op::T* __restrict__ dst,
+                                                              int64_t units, int Lmax, int U, uint4 pad16) {
+  typedef typename Op::T T;
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= units) return;
+  const int64_t r = idx / U;
+  const int c = (int)(idx - r * U);
+  const int b = (int)(r / Lmax), i = (int)(r - (int64_t)b * Lmax);
+  const int64_t s = table_row(b, i, Lmax, row_start, n_docs, doc_index, src_row);
+  dst[idx] = s >= 0 ? Op::cvt(corpus[s * U + c]) : pad_as(pad16, (T*)nullptr);
+}
+
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
+struct RowTable {
+  const int32_t* src_row;  // [B, Lmax]
+};
+
 struct Args {
   const char* name;
   hipStream_t st;
@@ -281,7 +345,8 @@ struct Args {
   const int64_t* row_start;
   int n_docs;
   const int32_t* doc_index;
-  const SegTables* seg;  // null: mts_gather_pad
+  const SegTables* seg;  // mts_gather_segments
+  const RowTable* tab;   // mts_gather_rows; neither: mts_gather_pad
   void* dst;
   int64_t rows;
   int Lmax;
@@ -298,7 +363,14 @@ int launch(const Args& a, int U) {
   const int64_t blocks = wide ? (a.rows + per_block - 1) / per_block : (units + 255) / 256;
   MTS_UNSUPPORTED(blocks <= 0x7fffffffLL, "%s: %lld destination rows are more than one launch covers", a.name, (long long)a.rows);
   const dim3 grid((unsigned)blocks), block(wide ? WAVES_PER_BLOCK * MTS_WAVE : 256);
-  if (!a.seg) {
+  if (a.tab) {
+    if (wide)
+      hipLaunchKernelGGL(gather_tab_rows_kernel<Op>, grid, block, 0, a.st, (const S*)a.corpus, a.row_start, a.n_docs, a.doc_index,
+                         a.tab->src_row, (T*)a.dst, a.rows, a.Lmax, U, a.pad16);
+    else
+      hipLaunchKernelGGL(gather_tab_thin_kernel<Op>, grid, block, 0, a.st, (const S*)a.corpus, a.row_start, a.n_docs, a.doc_index,
+                         a.tab->src_row, (T*)a.dst, units, a.Lmax, U, a.pad16);
+  } else if (!a.seg) {
     if (wide)
       hipLaunchKernelGGL(gather_rows_kernel<Op>, grid, block, 0, a.st, (const S*)a.corpus, a.row_start, a.n_docs, a.doc_index, (T*)a.dst, a.rows,
                          a.Lmax, U, a.pad16);
@@ -324,15 +396,16 @@ int launch(const Args& a, int U) {
   return MTS_OK;
 }
 
-// Argument checks, the pad pattern and the access width: one body for both entry points.
+// Argument checks, the pad pattern and the access width: one body for the three entry points.
 int gather(const char* name, void* stream, int src_dtype, int dst_dtype, int B, int Lmax, int D, const void* corpus, const int64_t* row_start,
-           int n_docs, const int32_t* doc_index, const SegTables* seg, void* dst, float pad_value) {
+           int n_docs, const int32_t* doc_index, const SegTables* seg, const RowTable* tab, void* dst, float pad_value) {
   MTS_CHECK_ARG((src_dtype == MTS_F32 || src_dtype == MTS_BF16) && (dst_dtype == MTS_F32 || dst_dtype == MTS_BF16),
                 "%s: dtypes must be fp32 or bf16 (got %d -> %d)", name, src_dtype, dst_dtype);
   MTS_CHECK_ARG(B >= 0 && Lmax >= 1 && D >= 1 && n_docs >= 1, "%s: bad shape (B %d, Lmax %d, D %d, n_docs %d)", name, B, Lmax, D, n_docs);
   MTS_CHECK_ARG(!seg || seg->n_listed >= 0, "%s: bad shape (n_listed %d)", name, seg ? seg->n_listed : 0);
   if (B == 0) return MTS_OK;
   MTS_CHECK_ARG(corpus && row_start && doc_index && dst, "%s: null pointer", name);
+  MTS_CHECK_ARG(!tab || tab->src_row, "%s: null row table", name);
   MTS_CHECK_ARG(!seg || (seg->ptr && seg->dst_len && (seg->n_listed == 0 || (seg->dst_off && seg->src_off))), "%s: null segment table", name);
   MTS_CHECK_ARG(!seg || !seg->close_last || (D == 1 && src_dtype == MTS_F32 && dst_dtype == MTS_F32),
                 "%s: close_last (the label rule) takes D = 1 in fp32 only (got D %d, %d -> %d)", name, D, src_dtype, dst_dtype);
@@ -343,7 +416,7 @@ int gather(const char* name, void* stream, int src_dtype, int dst_dtype, int B, 
     const uint32_t h = bf16_bits_rne(pbits) & 0xffffu;
     pbits = h | (h << 16);
   }
-  const Args a = {name, (hipStream_t)stream, corpus, row_start, n_docs, doc_index, seg, dst, (int64_t)B * Lmax, Lmax,
+  const Args a = {name, (hipStream_t)stream, corpus, row_start, n_docs, doc_index, seg, tab, dst, (int64_t)B * Lmax, Lmax,
                   make_uint4(pbits, pbits, pbits, pbits)};
   const uintptr_t sa = (uintptr_t)corpus, da = (uintptr_t)dst;
   MTS_CHECK_ARG((sa & (src_dtype == MTS_F32 ? 3 : 1)) == 0 && (da & (dst_dtype == MTS_F32 ? 3 : 1)) == 0,
@@ -367,7 +440,13 @@ int gather(const char* name, void* stream, int src_dtype, int dst_dtype, int B, 
 
 extern "C" int mts_gather_pad(void* stream, int src_dtype, int dst_dtype, int B, int Lmax, int D, const void* corpus, const int64_t* row_start,
                               int n_docs, const int32_t* doc_index, void* dst, float pad_value) {
-  return gather("mts_gather_pad", stream, src_dtype, dst_dtype, B, Lmax, D, corpus, row_start, n_docs, doc_index, nullptr, dst, pad_value);
+  return gather("mts_gather_pad", stream, src_dtype, dst_dtype, B, Lmax, D, corpus, row_start, n_docs, doc_index, nullptr, nullptr, dst, pad_value);
+}
+
+extern "C" int mts_gather_rows(void* stream, int src_dtype, int dst_dtype, int B, int Lmax, int D, const void* corpus, const int64_t* row_start,
+                               int n_docs, const int32_t* doc_index, const int32_t* src_row, void* dst, float pad_value) {
+  const RowTable tab = {src_row};
+  return gather("mts_gather_rows", stream, src_dtype, dst_dtype, B, Lmax, D, corpus, row_start, n_docs, doc_index, nullptr, &tab, dst, pad_value);
 }
 
 extern "C" int mts_gather_segments(void* stream, int src_dtype, int dst_dtype, int B, int Lmax, int D, const void* corpus,
@@ -375,5 +454,6 @@ extern "C" int mts_gather_segments(void* stream, int src_dtype, int dst_dtype, i
                                    const int32_t* seg_dst, const int32_t* seg_src, int n_listed, const int32_t* dst_len,
                                    const int32_t* close_last, void* dst, float pad_value) {
   const SegTables seg = {seg_ptr, seg_dst, seg_src, dst_len, close_last, n_listed};
-  return gather("mts_gather_segments", stream, src_dtype, dst_dtype, B, Lmax, D, corpus, row_start, n_docs, doc_index, &seg, dst, pad_value);
+  return gather("mts_gather_segments", stream, src_dtype, dst_dtype, B, Lmax, D, corpus, row_start, n_docs, doc_index, &seg, nullptr, dst,
+                pad_value);
 }

@@ -104,12 +104,16 @@ def _sum_over_ranks(values, trainer):
 
 
 def fit(trainer, train, val=None, *, batch_size, max_epochs, search_threshold=False, metric='Pk', thresholds=None, end_boundary=False,
-        patience=None, lr_factor=0.8, lr_patience=10, seed=0, shuffle=True, restore_best=True, on_epoch_end=None, augment=None):
+        patience=None, lr_factor=0.8, lr_patience=10, seed=0, shuffle=True, restore_best=True, on_epoch_end=None, augment=None, mask_inner=None):
     """-> {'epochs': [{'epoch', 'train_loss', 'monitored', 'lr' (the epoch's), 'threshold', + 'val_loss' or best(metric)'s row}, ...],
     'best_epoch', 'best_value', 'threshold' (the best epoch's), 'stopped_early'}; the same values on every rank.  ``on_epoch_end(record)``
     is called on every rank, after the epoch's threshold and learning rate are set and before the best state is restored.  ``augment``:
     None, or 'reverse' / 'shuffle' to train on ``train.augmented(augment, seed=seed)`` (resident.AugmentedCorpus: every document and a twin
-    with its topic segments reordered, 'shuffle' anew every epoch); validation never augments."""
+    with its topic segments reordered, 'shuffle' anew every epoch); validation never augments.  ``mask_inner``: None, or the probability
+    that a negative sentence is KEPT, to train on ``train.masked(mask_inner, seed=seed)`` (resident.MaskedCorpus: negative-sentence masking,
+    drawn anew every epoch); validation never masks.  The two views do not compose: both at once is a ValueError."""
+    if augment is not None and mask_inner is not None:
+        raise ValueError('fit: augment= and mask_inner= cannot be combined (the two corpus views do not compose)')
     model = trainer.model
     world = trainer.world
     rank = dist.get_rank(trainer.pg) if world > 1 else 0
@@ -122,6 +126,8 @@ def fit(trainer, train, val=None, *, batch_size, max_epochs, search_threshold=Fa
     mode = monitor_mode(search_threshold and val is not None, metric)
     if augment is not None:
         train = train.augmented(augment, seed=seed)
+    if mask_inner is not None:
+        train = train.masked(mask_inner, seed=seed)
     sampler = train.sampler(batch_size, rank=rank, world=world, shuffle=shuffle, seed=seed)
     if len(sampler) == 0:
         raise ValueError('fit: the training corpus gives no batch (fewer documents in every global batch than ranks)')

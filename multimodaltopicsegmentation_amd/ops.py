@@ -234,6 +234,39 @@ def gather_segments(corpus, row_start, doc_index, seg_ptr, seg_dst, seg_src, dst
     return dst
 
 
+def mask_plan(targets, row_start, doc_index, doc_seed, keep_probability, src_row, kept):
+    """the plan of a batch of masked documents (include/mts.h mts_mask_plan): for batch row b, the rows of document doc_index[b] (int32 [B])
+    that negative-sentence masking keeps -- a row whose fp32 target is not 0, or whose hash under doc_seed[b] (int64 [B] holding the uint64
+    bits) falls below keep_probability * 2^32; row 0 when none does -- are listed in order in src_row[b] (int32 [B, Lmax], -1 behind them)
+    and counted in kept[b] (int32 [B], not clipped to Lmax).  Every element of both is written.  -> (src_row, kept)"""
+    B, Lmax = int(src_row.shape[0]), int(src_row.shape[1])
+    assert targets.dtype == torch.float32 and targets.dim() == 1 and targets.is_contiguous()
+    assert row_start.dtype == torch.int64 and row_start.is_contiguous() and row_start.numel() >= 2
+    assert doc_index.dtype == torch.int32 and doc_index.is_contiguous() and doc_index.numel() == B
+    assert doc_seed.dtype == torch.int64 and doc_seed.is_contiguous() and doc_seed.numel() == B
+    assert src_row.dtype == torch.int32 and src_row.is_contiguous() and kept.dtype == torch.int32 and kept.is_contiguous() and kept.numel() == B
+    assert targets.device == row_start.device == doc_index.device == doc_seed.device == src_row.device == kept.device
+    check(lib.mts_mask_plan(stream_ptr(), B, Lmax, ptr(targets), ptr(row_start), row_start.numel() - 1, ptr(doc_index), ptr(doc_seed),
+                            float(keep_probability), ptr(src_row), ptr(kept)))
+    return src_row, kept
+
+
+def gather_rows(corpus, row_start, doc_index, src_row, dst, pad_value=0.0):
+    """gather_pad with a row table in front of the source row (include/mts.h mts_gather_rows): dst[b, t] = row src_row[b, t] (int32
+    [B, Lmax], on the device) of document doc_index[b]; a negative entry or one outside the document gives a pad row.  Every element of dst
+    is written."""
+    B, Lmax = int(dst.shape[0]), int(dst.shape[1])
+    D = 1 if corpus.dim() == 1 else int(corpus.shape[1])
+    assert dst.numel() == B * Lmax * D and dst.is_contiguous() and corpus.is_contiguous()
+    assert row_start.dtype == torch.int64 and row_start.is_contiguous() and row_start.numel() >= 2
+    assert doc_index.dtype == torch.int32 and doc_index.is_contiguous() and doc_index.numel() == B
+    assert src_row.dtype == torch.int32 and src_row.is_contiguous() and tuple(src_row.shape) == (B, Lmax)
+    assert corpus.device == dst.device == row_start.device == doc_index.device == src_row.device
+    check(lib.mts_gather_rows(stream_ptr(), dtype_code(corpus.dtype), dtype_code(dst.dtype), B, Lmax, D, ptr(corpus), ptr(row_start),
+                              row_start.numel() - 1, ptr(doc_index), ptr(src_row), ptr(dst), float(pad_value)))
+    return dst
+
+
 def embed_layernorm_fwd(x, pos, pos_offset, type0, gamma, beta, eps, y, pre, mean, rstd, row_src=None, x2=None):
     """row_src (int32 [n_rows], optional): packed batch -- output row r is sentence row_src[r] = b*L + i of x.
     x2 (fp32 [B, L, D2], optional): K-split input -- the row is x[b, i] | x2[b, i] and the concatenation is never materialised."""

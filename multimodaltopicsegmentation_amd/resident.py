@@ -20,7 +20,11 @@ at D = 1792, 238 MB in fp32, against 288 GB), so the fastest host collater is no
   * ``corpus.batch_segments(indices, orders, close_last)`` is ``batch()`` with every document's topic segments in a listed order, and
     ``corpus.augmented('reverse' | 'shuffle')`` an ``AugmentedCorpus``: a view with a reordered twin of every document (segment-order
     augmentation, the reference's ``inverse_augmentation``) made by the gather itself (``ops.gather_segments``, the same file): the same
-    bytes moved, no second copy of the corpus, a few hundred more integers in the per-call copy.
+    bytes moved, no second copy of the corpus, a few hundred more integers in the per-call copy;
+  * ``corpus.batch_masked(indices, doc_seeds, mask_probability)`` is ``batch()`` with a random share of every document's negative
+    sentences dropped, and ``corpus.masked(mask_probability, seed)`` a ``MaskedCorpus``: a view whose documents are masked anew every
+    epoch (negative-sentence masking, the reference's ``--mask_inner_sentences``).  ``ops.mask_plan`` (csrc/mask_plan.hip) draws and
+    compacts on the device, ``ops.gather_rows`` builds the tensors from its row table: two more integers per document in the per-call copy.
 
 For every tagger but ``SwitchBiLSTM(switch='dense')`` (see ``trainer.shard_batch``), ``corpus.batch(*item)`` on rank r holds the bits of
 ``shard_batch(collated global batch, r, world)``.  ``NativeTrainer.step`` takes these batches as they are.
@@ -30,6 +34,36 @@ import torch
 
 _WIRE = {'fp32': torch.float32, 'bf16': torch.bfloat16}
 _RING_SLOTS = 16
+_M64 = (1 << 64) - 1
+
+
+def _hash32(seed, idx):
+    """mts_hash32(seed, idx) of csrc/common.h (the counter hash of the dropout kernels) over uint64 arrays -> uint64 array holding the
+    32-bit values; ``seed`` is one value or an array of ``idx``'s shape"""
+    seed, idx = np.asarray(seed, dtype=np.uint64), np.asarray(idx, dtype=np.uint64)
+    with np.errstate(over='ignore'):
+        z = seed + np.uint64(0x9E3779B97F4A7C15) * (idx + np.uint64(1))
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z = z ^ (z >> np.uint64(31))
+    return z >> np.uint64(32)
+
+
+def mask_doc_seeds(seed, epoch, n_docs, docs=None):
+    """uint64 seeds of the masking draws of documents ``docs`` (None: all of them) in ``epoch``:
+    (mts_hash32(seed, 2c) << 32) | mts_hash32(seed, 2c + 1) with c = epoch * n_docs + d, in 64-bit wrapping arithmetic"""
+    d = np.arange(n_docs, dtype=np.uint64) if docs is None else np.asarray(docs, dtype=np.int64).astype(np.uint64)
+    with np.errstate(over='ignore'):
+        c2 = (np.uint64((int(epoch) * int(n_docs)) & _M64) + d) * np.uint64(2)
+        s = np.uint64(int(seed) & _M64)
+        return (_hash32(s, c2) << np.uint64(32)) | _hash32(s, c2 + np.uint64(1))
+
+
+def _keep_probability(p, who):
+    p = float(p)
+    if not 0.0 <= p <= 1.0:                                                        # a NaN fails both comparisons
+        raise ValueError(f'{who}: mask_probability is the probability that a negative sentence is KEPT and lies in [0, 1], not {p}')
+    return p
 
 
 def _rows_2d(items, what):
@@ -103,6 +137,9 @@ class ResidentCorpus:
         self.corpus2 = upload(emb2) if emb2 is not None else None
         self.targets = torch.cat(tgt).contiguous().to(self.device)
         self.row_start = torch.from_numpy(start).to(self.device)
+        # host copies of the labels and the row table (4 bytes per sentence): the host half of negative-sentence masking draws from them
+        self._labels_host = torch.cat(tgt).numpy().copy()
+        self._start_host = start
         self._ring = None
         self._turn = 0
 
@@ -300,6 +337,111 @@ class ResidentCorpus:
         """-> AugmentedCorpus(self, mode, seed): 2 x n_docs virtual documents, every stored one and its twin with the segments reordered"""
         return AugmentedCorpus(self, mode, seed=seed)
 
+    # ---- negative-sentence masking -------------------------------------------------------------------------------------------
+    def _mask_plan_host(self, ii, seeds, p):
+        """the host's plan of masking documents ``ii`` under ``seeds`` (uint64, one per listed document): the rule of mts_mask_plan
+        (include/mts.h) in one vectorised pass over the listed documents' labels -> (kept rows per document [B], the kept rows' indices
+        inside their documents, concatenated, where every document's start in that list [B + 1], the kept rows' labels)"""
+        B = int(ii.size)
+        rows = self.rows[ii]
+        ptr = np.zeros(B + 1, dtype=np.int64)
+        np.cumsum(rows, out=ptr[1:])
+        which = np.repeat(np.arange(B, dtype=np.int64), rows)
+        rel = np.arange(int(ptr[-1]), dtype=np.int64) - ptr[which]
+        y = self._labels_host[self._start_host[ii][which] + rel]
+        keep = (y != 0) | (_hash32(seeds[which], rel) < np.uint64(min(int(p * 4294967296.0), 1 << 32)))
+        seen = np.concatenate([[0], np.cumsum(keep)])
+        counts = (seen[ptr[1:]] - seen[ptr[:-1]]).astype(np.int64)
+        empty = (counts == 0) & (rows > 0)
+        if empty.any():                                                   # the empty-draw rule: row 0 of such a document stays
+            keep[ptr[:-1][empty]] = True
+            counts[empty] = 1
+        flat = np.flatnonzero(keep)
+        kept_ptr = np.zeros(B + 1, dtype=np.int64)
+        np.cumsum(counts, out=kept_ptr[1:])
+        return counts, rel[flat], kept_ptr, y[flat]
+
+    def _masked_segment_ends(self, counts, kept_ptr, kept_labels):
+        """src_segments of masked documents: the positions just behind the kept rows that are boundaries, inside the reported length"""
+        lengths = np.minimum(counts, self.tv) if self.truncate else counts
+        return [(np.flatnonzero(kept_labels[int(s):int(s) + int(n)] == 1) + 1).tolist() for s, n in zip(kept_ptr[:-1], lengths)]
+
+    def _masked_host_fields(self, ii, counts, segment_ends, pad_to):
+        lengths = np.minimum(counts, self.tv) if self.truncate else counts
+        if self.truncate:
+            if pad_to is not None:
+                raise ValueError('pad_to cannot be combined with truncate=True (every batch is truncate_value long)')
+            Lmax = self.tv
+        else:
+            Lmax = int(counts.max())
+            if pad_to is not None:
+                if int(pad_to) < Lmax:
+                    raise ValueError(f'pad_to {int(pad_to)} is shorter than the longest masked document ({Lmax})')
+                Lmax = int(pad_to)
+        out = {'id': torch.from_numpy(ii.copy()), 'src_lengths': torch.from_numpy(lengths.astype(np.int64, copy=True)),
+               'domain': [self.domain[i] for i in ii.tolist()] if self.da else None}
+        if self.segments:
+            out['src_segments'] = [list(s) for s in segment_ends]
+        return out, Lmax
+
+    def batch_masked(self, indices, doc_seeds, mask_probability, pad_to=None, lengths=None, segment_ends=None, return_plan=False):
+        """``batch()`` of documents ``indices`` with a random share of their negative sentences dropped (negative-sentence masking, the
+        reference's ``--mask_inner_sentences``, utils/load_datasets_precomputed.py:174-185, moved into the gather).
+
+        Row r of document ``indices[k]`` stays when its label is not 0 or when ``mts_hash32(doc_seeds[k], r) < mask_probability * 2^32``:
+        ``mask_probability`` is the probability that a negative sentence is KEPT (the reference's code, not its help text); a document
+        none of whose rows stays keeps row 0.  The kept rows move up in order; embeddings, second input and labels travel together and the
+        labels are not rewritten.  ``doc_seeds``: one uint64 per listed document (``mask_doc_seeds``).  ``src_lengths`` are the kept
+        lengths (cut at truncate_value by a truncate=True corpus, as a stored document is), ``src_segments`` the positions behind the
+        kept boundaries inside them.  Same keys, dtypes and devices as ``batch()``.
+
+        ``lengths`` (and ``segment_ends`` for a segments=True corpus): the kept rows per listed document (and their 'src_segments') when
+        the caller already has them -- MaskedCorpus does, from its plan of the epoch, and then nothing O(sentences) runs on the host here.
+        Without them they are computed from the host copy of the listed documents' labels.  The device never reports them back in this
+        path; ``return_plan=True`` returns ``(batch, src_row, kept)`` with the device's int32 plan [B, Lmax] and counts [B] next to it.
+
+        One ``ops.mask_plan`` launch and one ``ops.gather_rows`` launch per tensor on the current stream; the seeds travel with the indices
+        in ONE asynchronous copy out of the pinned ring.  ValueError for a mask_probability outside [0, 1], a seed list of another length
+        and a pad_to below the longest masked document; IndexError for an index outside the corpus."""
+        ii = self._indices(indices)
+        p = _keep_probability(mask_probability, 'batch_masked')
+        if ii.size == 0:
+            return ({}, None, None) if return_plan else {}
+        B = int(ii.size)
+        seeds = np.ascontiguousarray(np.asarray(doc_seeds, dtype=np.uint64).reshape(-1))
+        if seeds.size != B:
+            raise ValueError(f'batch_masked: {B} documents but {seeds.size} seeds')
+        if lengths is None:
+            counts, _, kept_ptr, kept_labels = self._mask_plan_host(ii, seeds, p)
+            segment_ends = self._masked_segment_ends(counts, kept_ptr, kept_labels) if self.segments else None
+        else:
+            counts = np.asarray(lengths, dtype=np.int64).reshape(-1)
+            if counts.size != B or (self.segments and (segment_ends is None or len(segment_ends) != B)):
+                raise ValueError(f'batch_masked: lengths (and segment_ends of a segments=True corpus) are one per listed document ({B})')
+        out, Lmax = self._masked_host_fields(ii, counts, segment_ends, pad_to)
+        if self.device.type != 'cuda':
+            raise RuntimeError('ResidentCorpus.batch_masked gathers on the GPU (there is no CPU fallback)')
+        from . import ops
+        with torch.cuda.device(self.device):
+            # the seeds first: their 8-byte alignment is the allocation's
+            dev = self._upload_indices(np.concatenate([seeds.view(np.int32).astype(np.int64), ii]))
+            seed_dev, idx = dev[:2 * B].view(torch.int64), dev[2 * B:]
+            src_row, kept = ops.mask_plan(self.targets, self.row_start, idx, seed_dev, p,
+                                          torch.empty((B, Lmax), dtype=torch.int32, device=self.device),
+                                          torch.empty(B, dtype=torch.int32, device=self.device))
+
+            def gather(corpus, dst, **kw):
+                return ops.gather_rows(corpus, self.row_start, idx, src_row, dst, **kw)
+            out['src_tokens'] = gather(self.corpus, torch.empty((B, Lmax, self.corpus.shape[1]), dtype=self.wire, device=self.device))
+            out['src_tokens2'] = None if self.corpus2 is None else gather(
+                self.corpus2, torch.empty((B, Lmax, self.corpus2.shape[1]), dtype=self.wire, device=self.device))
+            out['tgt_tokens'] = gather(self.targets, torch.empty((B, Lmax), dtype=torch.float32, device=self.device), pad_value=0.0 - self.minus)
+        return (out, src_row, kept) if return_plan else out
+
+    def masked(self, mask_probability=0.9, seed=0):
+        """-> MaskedCorpus(self, mask_probability, seed): the n_docs documents with negative sentences dropped, drawn anew every epoch"""
+        return MaskedCorpus(self, mask_probability, seed=seed)
+
 
 class AugmentedCorpus:
     """A view of a ResidentCorpus with ``2 * n_docs`` virtual documents: index v < n_docs is stored document v, bit for bit what
@@ -393,6 +535,72 @@ class AugmentedCorpus:
         return _AugmentedSampler(self, 2 * self.n_docs if self.corpus.truncate else self.lengths, batch_size, **kw)
 
 
+class MaskedCorpus:
+    """A view of a ResidentCorpus whose ``n_docs`` documents have a random share of their NEGATIVE sentences dropped (negative-sentence
+    masking; reference: ``--mask_inner_sentences`` / ``--mask_probability``, utils/load_datasets_precomputed.py:174-185), made by the plan
+    kernel and the gather (``ResidentCorpus.batch_masked``) and drawn anew every epoch.  Nothing is copied and nothing is uploaded again.
+
+    ``mask_probability`` is the probability that a negative sentence is KEPT -- the reference's code (`rand() > mask_probability and not
+    label` drops) and ``datasets.load_dataset_from_precomputed``'s reading of it, not the reference's help text: 1.0 keeps everything, 0.0
+    keeps the boundaries alone.  Document d's draw in an epoch hangs on ``mask_doc_seeds(seed, epoch, n_docs)[d]`` only: every rank and
+    the host regenerate it without a collective.  A document none of whose rows is kept keeps row 0 (the reference would make an empty one).
+
+    ``set_epoch(e)`` makes the epoch's host plan once -- one vectorised pass of the device's hash over the corpus' host labels, O(sentences)
+    per EPOCH -- and keeps it until the epoch changes: ``rows`` / ``lengths`` (what a batch reports; cut at truncate_value by a
+    truncate=True corpus), the ``src_segments`` and the ``pad_to`` of the view's sampler come from it, so a step does nothing
+    O(sentences) on the host and reads nothing back from the device.  ``host_fields`` (no GPU), ``batch``, ``sampler``, ``__len__`` and
+    ``lengths`` mirror the corpus'; ``'id'`` and ``'domain'`` are the stored document's."""
+
+    def __init__(self, corpus, mask_probability=0.9, seed=0):
+        self.mask_probability = _keep_probability(mask_probability, 'MaskedCorpus')
+        self.corpus, self.seed, self.epoch = corpus, int(seed), None
+        self.n_docs = corpus.n_docs
+        self.set_epoch(0)
+
+    def __len__(self):
+        return self.n_docs
+
+    def set_epoch(self, epoch):
+        """the epoch of the draws; the host plan is made here, once per epoch"""
+        epoch = int(epoch)
+        if epoch == self.epoch:
+            return
+        c = self.corpus
+        self.doc_seeds = mask_doc_seeds(self.seed, epoch, self.n_docs)
+        self.rows, self._kept_rel, self._kept_ptr, kept_labels = c._mask_plan_host(np.arange(self.n_docs, dtype=np.int64), self.doc_seeds,
+                                                                                   self.mask_probability)
+        self.lengths = np.minimum(self.rows, c.tv) if c.truncate else self.rows.copy()
+        self._segment_ends = c._masked_segment_ends(self.rows, self._kept_ptr, kept_labels) if c.segments else None
+        self.epoch = epoch
+
+    def kept_rows(self, d):
+        """the host plan of document d in this epoch: the indices of its kept rows, ascending (what the device's src_row lists)"""
+        return self._kept_rel[int(self._kept_ptr[d]):int(self._kept_ptr[d + 1])].copy()
+
+    def _plan_of(self, ii):
+        return self.rows[ii], [self._segment_ends[i] for i in ii.tolist()] if self._segment_ends is not None else None
+
+    def host_fields(self, indices, pad_to=None):
+        """the host half of ``batch()``: ({'id', 'src_lengths', 'domain'(, 'src_segments')}, padded length); touches no GPU"""
+        ii = self.corpus._indices(indices)
+        if ii.size == 0:
+            return {}, 0
+        return self.corpus._masked_host_fields(ii, *self._plan_of(ii), pad_to)
+
+    def batch(self, indices, pad_to=None):
+        """the batch dict of the masked documents ``indices`` in this epoch: one ``corpus.batch_masked`` call with the plan's lengths"""
+        ii = self.corpus._indices(indices)
+        if ii.size == 0:
+            return {}
+        counts, ends = self._plan_of(ii)
+        return self.corpus.batch_masked(ii, self.doc_seeds[ii], self.mask_probability, pad_to=pad_to, lengths=counts, segment_ends=ends)
+
+    def sampler(self, batch_size, **kw):
+        """a DocumentShardSampler over the masked documents whose ``set_epoch`` also moves this view to the epoch and takes ``pad_to``
+        from the epoch's masked lengths: every rank pads a global batch to the same length without a collective"""
+        return _MaskedSampler(self, batch_size, **kw)
+
+
 class DocumentShardSampler:
     """Rank-local batch sampler for data-parallel training from a ResidentCorpus.
 
@@ -461,3 +669,18 @@ class _AugmentedSampler(DocumentShardSampler):
     def set_epoch(self, epoch):
         super().set_epoch(epoch)
         self.view.set_epoch(epoch)
+
+
+class _MaskedSampler(DocumentShardSampler):
+    """MaskedCorpus.sampler: the epoch also reaches the view, and ``pad_to`` follows the epoch's masked lengths"""
+
+    def __init__(self, view, batch_size, **kw):
+        super().__init__(view.n_docs if view.corpus.truncate else view.lengths, batch_size, **kw)
+        self.view = view
+        self.set_epoch(self.epoch)
+
+    def set_epoch(self, epoch):
+        super().set_epoch(epoch)
+        self.view.set_epoch(epoch)
+        if self.lengths is not None:
+            self.lengths = self.view.lengths

@@ -21,6 +21,11 @@ segment_augment_bench.txt), same rules:
     AugmentedCorpus; a fresh index list and fresh tables per call, uploaded beforehand.  Both kernels move the same bytes.
 (b) NativeTrainer.step of the configs[1] transformer fed by ResidentCorpus + sampler and by AugmentedCorpus('shuffle') + its sampler, and
     the host half of one augmented batch (drawing the orders, building the tables) timed on its own.
+
+--mask runs the legs of negative-sentence masking INSTEAD (DESIGN.md §3 "Negative-sentence masking"; out: profiles/mask_inner_bench.txt),
+same rules: the launches of one late-fusion batch of 64 documents of 256 rows (1792 + 1792 bf16 and the targets) -- mts_mask_plan and
+three mts_gather_rows at keep probability 0.9 and 1.0 -- next to the plain batch's three mts_gather_pad of the same kind of index list,
+in microseconds and as a ratio to the plain batch; the plan kernel alone; the host half of a masked batch and MaskedCorpus.set_epoch.
 """
 import argparse
 import json
@@ -279,9 +284,97 @@ def segment_step_legs(corpus, steps, warmup, reps, say):
             'draw_us': round(draw, 1)}
 
 
+def mask_legs(corpus, iters, reps, say):
+    """--mask: the kernels of a masked late-fusion batch (mts_mask_plan + three mts_gather_rows) next to the plain batch's (three
+    mts_gather_pad) of the same documents, and the two host halves"""
+    import numpy as np
+    from multimodaltopicsegmentation_amd.resident import mask_doc_seeds
+    g = torch.Generator().manual_seed(1)
+    lists = torch.randint(0, N_DOCS, (iters + 8, B), generator=g).numpy().astype(np.int64)
+    D2 = int(corpus.corpus2.shape[1])
+    big = {name: torch.empty(B * L * w, dtype=dt, device=DEV) for name, w, dt in (('a', D, torch.bfloat16), ('b', D2, torch.bfloat16), ('t', 1, torch.float32))}
+    table, kept = torch.empty(B * L, dtype=torch.int32, device=DEV), torch.empty(B, dtype=torch.int32, device=DEV)
+
+    def prepared(p):
+        out = []
+        for k, ii in enumerate(lists):
+            seeds = mask_doc_seeds(5, k, N_DOCS, ii)
+            Lmax = int(corpus._mask_plan_host(ii, seeds, p)[0].max())
+            out.append((torch.from_numpy(ii).to(torch.int32).to(DEV), torch.from_numpy(seeds.view(np.int64).copy()).to(DEV), Lmax))
+        return out
+    prep = {0.9: prepared(0.9), 1.0: prepared(1.0)}
+
+    def plain(k):
+        idx = prep[1.0][k % len(lists)][0]
+        ops.gather_pad(corpus.corpus, corpus.row_start, idx, big['a'].view(B, L, D))
+        ops.gather_pad(corpus.corpus2, corpus.row_start, idx, big['b'].view(B, L, D2))
+        ops.gather_pad(corpus.targets, corpus.row_start, idx, big['t'].view(B, L), pad_value=-1.0)
+
+    def plan(p, k):
+        idx, seeds, Lmax = prep[p][k % len(lists)]
+        return idx, Lmax, ops.mask_plan(corpus.targets, corpus.row_start, idx, seeds, p, table[:B * Lmax].view(B, Lmax), kept)[0]
+
+    def masked(p, k):
+        idx, Lmax, rows = plan(p, k)
+        ops.gather_rows(corpus.corpus, corpus.row_start, idx, rows, big['a'][:B * Lmax * D].view(B, Lmax, D))
+        ops.gather_rows(corpus.corpus2, corpus.row_start, idx, rows, big['b'][:B * Lmax * D2].view(B, Lmax, D2))
+        ops.gather_rows(corpus.targets, corpus.row_start, idx, rows, big['t'][:B * Lmax].view(B, Lmax), pad_value=-1.0)
+    # every leg takes ANOTHER index list in the same trip, so that none finds the rows its predecessor has just pulled into the caches
+    legs = {'plain batch: 3 x mts_gather_pad': plain,
+            'masked p = 0.9: mts_mask_plan + 3 x mts_gather_rows': lambda k: masked(0.9, k + 3),
+            'masked p = 1.0: mts_mask_plan + 3 x mts_gather_rows': lambda k: masked(1.0, k + 5),
+            'mts_mask_plan alone, p = 0.9': lambda k: plan(0.9, k + 6),
+            'plain batch, once more (last in the trip)': lambda k: plain(k + 7)}
+    for k in range(8):                                                                      # warm every leg
+        for f in legs.values():
+            f(k)
+    torch.cuda.synchronize()
+    out = {name: [] for name in legs}
+    for _ in range(reps):
+        ev = {name: [] for name in legs}
+        for k in range(iters):
+            for name, f in legs.items():
+                s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                s.record()
+                f(k)
+                e.record()
+                ev[name].append((s, e))
+        torch.cuda.synchronize()
+        for name in legs:
+            out[name].append(median([s.elapsed_time(e) * 1e3 for s, e in ev[name]]))
+    mean_L = sum(t[2] for t in prep[0.9]) / len(lists)
+    say(f'(a) the launches of one batch between two device events, median of {iters} per repetition, the legs in turn; {B} documents of {L} rows, '
+        f'{D} + {D2} bf16 and the targets; padded length at p = 0.9: {mean_L:.1f} on average')
+    base = out['plain batch: 3 x mts_gather_pad']
+    res = {}
+    for name, us in out.items():
+        say(f'  {name:54s} ' + '  '.join(f'{t:7.1f} us' for t in us) + '   ratio to the plain batch ' + '  '.join(f'{t / b:5.3f}' for t, b in zip(us, base)))
+        res[name] = {'us': [round(t, 1) for t in us], 'ratio': [round(t / b, 3) for t, b in zip(us, base)]}
+    say(f'  table bytes of a masked batch: 4 x {B} x Lmax written by the plan and read by each of the three gathers ({4 * B * L} B at Lmax = {L}) '
+        f'next to {B * L * (2 * D + 2 * D2 + 4)} destination bytes; the plan reads 4 B per stored row ({4 * B * L} B)')
+    # the host halves: what the loop's host thread pays per step before it can launch anything, and the epoch's plan
+    view = corpus.masked(0.9, seed=5)
+    t0 = time.perf_counter()
+    for e in range(1, 6):
+        view.set_epoch(e)
+    per_epoch = 1e6 * (time.perf_counter() - t0) / 5
+    host = {}
+    for name, src in (('plain', corpus), ('masked', view)):
+        t0 = time.perf_counter()
+        for ii in lists[:iters]:
+            src.host_fields(ii)
+        host[name] = 1e6 * (time.perf_counter() - t0) / iters
+    say(f'  host half of one batch (host_fields, no launch): plain {host["plain"]:.0f} us, masked {host["masked"]:.0f} us; '
+        f'MaskedCorpus.set_epoch ({corpus.total_rows} sentences): {per_epoch:.0f} us per epoch')
+    res['host_us'] = {k: round(v, 1) for k, v in host.items()}
+    res['set_epoch_us'] = round(per_epoch, 1)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=None)
+    ap.add_argument('--mask', action='store_true', help='the legs of negative-sentence masking instead (mask_legs)')
     ap.add_argument('--segments', action='store_true', help='the legs of segment-order augmentation instead (module docstring)')
     ap.add_argument('--iters', type=int, default=200)
     ap.add_argument('--steps', type=int, default=150)
@@ -290,7 +383,7 @@ def main():
     a = ap.parse_args()
     if a.out is None:
         a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles',
-                             'segment_augment_bench.txt' if a.segments else 'resident_corpus_bench.txt')
+                             'mask_inner_bench.txt' if a.mask else 'segment_augment_bench.txt' if a.segments else 'resident_corpus_bench.txt')
     if not torch.cuda.is_available():
         sys.exit('resident_corpus_bench: no GPU visible; nothing is measured without one')
     lines = []
@@ -298,9 +391,13 @@ def main():
     def say(s):
         print(s, flush=True)
         lines.append(s)
-    say(f'tools/resident_corpus_bench.py {"--segments " if a.segments else ""}--iters {a.iters} --steps {a.steps} --warmup {a.warmup} --reps {a.reps}'
+    say(f'tools/resident_corpus_bench.py {"--mask " if a.mask else "--segments " if a.segments else ""}--iters {a.iters} --steps {a.steps} --warmup {a.warmup} --reps {a.reps}'
         f'   ({torch.cuda.get_device_name(0)})')
-    if a.segments:
+    if a.mask:
+        ds = AudioPortionDataset(_boundary_lines(torch.Generator().manual_seed(4321)), {'0': 0, '1': 1}, CRF=False, truncate=False,
+                                 second_input=_boundary_lines(torch.Generator().manual_seed(1234)))
+        res = {'mask': mask_legs(ResidentCorpus(ds, DEV, wire_dtype='bf16'), a.iters, a.reps, say)}
+    elif a.segments:
         ds = AudioPortionDataset(_boundary_lines(torch.Generator().manual_seed(4321)), {'0': 0, '1': 1}, CRF=False, truncate=False)
         corpus = ResidentCorpus(ds, DEV, wire_dtype='bf16')
         res = {'gather': segment_gather_legs(corpus, a.iters, a.reps, say)}
