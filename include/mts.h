@@ -239,6 +239,32 @@ int mts_gather_rows(void* stream, int src_dtype, int dst_dtype, int B, int Lmax,
                     const int32_t* src_row,      /* device [B, Lmax]: document-relative source row of every destination row */
                     void* dst,                   /* device [B, Lmax, D] in dst_dtype */
                     float pad_value);
+/* PCA PROJECTION OF THE RESIDENT CORPUS (pca.PcaReducer, ResidentCorpus.fit_pca / projected; reference: --pca_reduce / --pca_value,
+ * EncoderDataset.py:49-70): the moments of the fit and the transform, csrc/pca.hip.  x is the corpus as stored: dtype MTS_F32 | MTS_BF16,
+ * row-major [rows, D], contiguous, any alignment its dtype has.  All three run on the caller's stream, use no atomics, no workspace and no
+ * dependence between workgroups, write every output element exactly once and give the same bits for the same inputs.
+ * MTS_ERR_INVALID before any device work: an unknown dtype, a null pointer, rows < 1, D < 1, k outside 1 .. D;  MTS_ERR_UNSUPPORTED:
+ * D > 4096 (the fp64 Gram matrix is D * D * 8 bytes), and for mts_pca_project the pair bf16 -> fp32.
+ *   mts_pca_colsum   sum_out[d] = sum_r x[r, d] in fp64 (a thread adds every 16th row of a column, the 16 partial sums are added in order).
+ *   mts_pca_gram     gram_out[i, j] = sum_r z[r, i] z[r, j],  z[r, d] = fl32(x[r, d] - center[d]): the element is upcast to fp32 and the centre
+ *                    subtracted once, in fp32; products and sums on v_mfma_f32_32x32x2_f32 (exact fp32, a row-ordered fma chain); after
+ *                    every PCA_SLICE = 1024 rows the fp32 accumulators are added to fp64 ones and restarted, so
+ *                    |G - exact| <= (1024 + 4) 2^-24 sum_r |z_ri| |z_rj| elementwise at any number of rows.  One workgroup owns a 64 x 64
+ *                    tile on or above the diagonal for all rows and writes the tile and its mirror: gram_out is exactly symmetric.
+ *   mts_pca_project  y[r, j] = sum_d z[r, d] w[j, d] for j < k: the same staging, one fp32 fma chain over D on the same instruction, ONE
+ *                    rounding to out_dtype (fp32, or bf16 round-to-nearest-even).  fp32 -> fp32, bf16 -> bf16, fp32 -> bf16. */
+int mts_pca_colsum(void* stream, int dtype, int rows, int D,
+                   const void* x,               /* device [rows, D] */
+                   double* sum_out);            /* device [D] out */
+int mts_pca_gram(void* stream, int dtype, int rows, int D,
+                 const void* x,                 /* device [rows, D] */
+                 const float* center,           /* device [D] */
+                 double* gram_out);             /* device [D, D] out */
+int mts_pca_project(void* stream, int in_dtype, int out_dtype, int rows, int D, int k,
+                    const void* x,              /* device [rows, D] in in_dtype */
+                    const float* center,        /* device [D] */
+                    const float* w,             /* device [k, D], row-major: the components */
+                    void* y);                   /* device [rows, k] in out_dtype, out */
 
 /* ---------------------------------------------------------------------------------------------
  * LayerNorm family (biased variance, eps inside sqrt).

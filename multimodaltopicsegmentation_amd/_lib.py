@@ -129,6 +129,9 @@ SIGNATURES = {
     'mts_gather_segments': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _f]),
     'mts_mask_plan': (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, C.c_double, _vp, _vp]),
     'mts_gather_rows': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _f]),
+    'mts_pca_colsum': (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    'mts_pca_gram': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    'mts_pca_project': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
 }
 
 _missing = []

@@ -68,7 +68,8 @@ def load_dataset_from_precomputed(embedding_directory, lab_file, delete_last_sen
                                   mask_probability=0.9, split=None, timing_info=None, split_modalities=False):
     if inverse_augmentation or umap_project:
         raise NotImplementedError('inverse_augmentation / umap_project are outside the hot path (SURVEY.md §8f); segment-order augmentation is done '
-                                  "in the gather instead: ResidentCorpus.augmented('reverse' | 'shuffle')")
+                                  "in the gather instead: ResidentCorpus.augmented('reverse' | 'shuffle'), the PCA projection on the resident corpus: "
+                                  'ResidentCorpus.fit_pca / projected')
     standard_split = split is not None
     if standard_split:
         with open(split) as f:

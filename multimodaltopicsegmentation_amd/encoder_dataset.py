@@ -135,7 +135,8 @@ class AudioPortionDataset(Dataset):
                  umap_project_value=100, umap_class=None, second_input=None, domain_adapt=False, pin_memory=False, wire_dtype='fp32',
                  pin_slots=4, collate_threads=8, segments=False):
         if umap_project:
-            raise NotImplementedError('PCA/UMAP projection (EncoderDataset.py:49-69) is outside the hot path')
+            raise NotImplementedError('PCA/UMAP projection (EncoderDataset.py:49-69) is not done at load time: project the resident corpus, '
+                                      'ResidentCorpus.fit_pca / projected')
         # segments (extension, default False: the batch dict keeps the reference's keys): True adds 'src_segments', what TextSegmenter(
         # cosine_loss=True) reads and no collater of the reference makes -- per document the boundary positions [t + 1 for t < length if
         # target[t] == 1], so every listed segment ends with its boundary sentence and the rest of the document is the last negative
@@ -285,7 +286,7 @@ class AudioPortionDatasetInference(Dataset):
     def __init__(self, lines, encoder='x-vectors', CRF=True, truncate=False, truncate_value=100, umap_project=False,
                  umap_project_value=100, umap_class=None):
         if umap_project:
-            raise NotImplementedError('PCA/UMAP projection is outside the hot path')
+            raise NotImplementedError('PCA/UMAP projection is not done at load time: project the resident corpus, ResidentCorpus.fit_pca / projected')
         self.minus = 0 if CRF else 1
         self.embeddings = lines
         self.truncate, self.tv = truncate, truncate_value

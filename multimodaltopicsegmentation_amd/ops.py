@@ -267,6 +267,48 @@ def gather_rows(corpus, row_start, doc_index, src_row, dst, pad_value=0.0):
     return dst
 
 
+def _pca_matrix(x):
+    assert x.dim() == 2 and x.is_contiguous() and x.is_cuda, 'a contiguous [rows, D] device matrix is expected'
+    return int(x.shape[0]), int(x.shape[1])
+
+
+def pca_colsum(x, out=None):
+    """column sums of the fp32 / bf16 matrix x [rows, D] in fp64 (include/mts.h mts_pca_colsum) -> out (fp64 [D], every element written)"""
+    rows, D = _pca_matrix(x)
+    if out is None:
+        out = torch.empty(D, dtype=torch.float64, device=x.device)
+    assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() == D and out.device == x.device
+    check(lib.mts_pca_colsum(stream_ptr(), dtype_code(x.dtype), rows, D, ptr(x), ptr(out)))
+    return out
+
+
+def pca_gram(x, center, out=None):
+    """G = sum_r (x_r - center)(x_r - center)^T of the fp32 / bf16 matrix x [rows, D] about the fp32 centre [D] (include/mts.h mts_pca_gram):
+    centred in fp32, multiplied on the fp32 matrix cores, summed in fp64 across slices of 1024 rows -> out (fp64 [D, D], every element
+    written, exactly symmetric)"""
+    rows, D = _pca_matrix(x)
+    if out is None:
+        out = torch.empty((D, D), dtype=torch.float64, device=x.device)
+    assert center.dtype == torch.float32 and center.is_contiguous() and center.numel() == D
+    assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() == D * D and out.device == x.device == center.device
+    check(lib.mts_pca_gram(stream_ptr(), dtype_code(x.dtype), rows, D, ptr(x), ptr(center), ptr(out)))
+    return out
+
+
+def pca_project(x, center, w, y=None):
+    """y[r, j] = sum_d fl32(x[r, d] - center[d]) w[j, d] (include/mts.h mts_pca_project): x fp32 / bf16 [rows, D], center fp32 [D], w fp32
+    [k, D] -> y [rows, k] (x's dtype unless given: fp32 -> fp32, bf16 -> bf16, fp32 -> bf16; one rounding; every element written)"""
+    rows, D = _pca_matrix(x)
+    assert w.dim() == 2 and w.dtype == torch.float32 and w.is_contiguous() and int(w.shape[1]) == D
+    k = int(w.shape[0])
+    if y is None:
+        y = torch.empty((rows, k), dtype=x.dtype, device=x.device)
+    assert center.dtype == torch.float32 and center.is_contiguous() and center.numel() == D
+    assert y.is_contiguous() and y.numel() == rows * k and y.device == x.device == center.device == w.device
+    check(lib.mts_pca_project(stream_ptr(), dtype_code(x.dtype), dtype_code(y.dtype), rows, D, k, ptr(x), ptr(center), ptr(w), ptr(y)))
+    return y
+
+
 def embed_layernorm_fwd(x, pos, pos_offset, type0, gamma, beta, eps, y, pre, mean, rstd, row_src=None, x2=None):
     """row_src (int32 [n_rows], optional): packed batch -- output row r is sentence row_src[r] = b*L + i of x.
     x2 (fp32 [B, L, D2], optional): K-split input -- the row is x[b, i] | x2[b, i] and the concatenation is never materialised."""

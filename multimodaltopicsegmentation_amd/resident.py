@@ -24,7 +24,10 @@ at D = 1792, 238 MB in fp32, against 288 GB), so the fastest host collater is no
   * ``corpus.batch_masked(indices, doc_seeds, mask_probability)`` is ``batch()`` with a random share of every document's negative
     sentences dropped, and ``corpus.masked(mask_probability, seed)`` a ``MaskedCorpus``: a view whose documents are masked anew every
     epoch (negative-sentence masking, the reference's ``--mask_inner_sentences``).  ``ops.mask_plan`` (csrc/mask_plan.hip) draws and
-    compacts on the device, ``ops.gather_rows`` builds the tensors from its row table: two more integers per document in the per-call copy.
+    compacts on the device, ``ops.gather_rows`` builds the tensors from its row table: two more integers per document in the per-call copy;
+  * ``corpus.fit_pca(n_components)`` fits a ``pca.PcaReducer`` on the resident rows (the reference's ``--pca_reduce``; moments by
+    ``ops.pca_colsum`` / ``ops.pca_gram``, csrc/pca.hip) and ``corpus.projected(reducer)`` is the corpus at width k (``ops.pca_project``):
+    every method above reads the width from the matrix and takes it as it is.
 
 For every tagger but ``SwitchBiLSTM(switch='dense')`` (see ``trainer.shard_batch``), ``corpus.batch(*item)`` on rank r holds the bits of
 ``shard_batch(collated global batch, r, world)``.  ``NativeTrainer.step`` takes these batches as they are.
@@ -441,6 +444,53 @@ class ResidentCorpus:
     def masked(self, mask_probability=0.9, seed=0):
         """-> MaskedCorpus(self, mask_probability, seed): the n_docs documents with negative sentences dropped, drawn anew every epoch"""
         return MaskedCorpus(self, mask_probability, seed=seed)
+
+    # ---- PCA projection --------------------------------------------------------------------------------------------------------
+    def fit_pca(self, n_components=167, field='embeddings', return_moments=False):
+        """-> pca.PcaReducer fitted on ALL rows of this corpus' first (``field='embeddings'``) or second (``'embeddings2'``) input (the
+        reference's ``--pca_reduce``: sklearn's PCA(n_components) on the training split, EncoderDataset.py:49-70; it projects the first
+        input only).  On the device: ``ops.pca_colsum`` -> centre = fp32(colsum / N) -> ``ops.pca_gram``; on the host
+        ``pca.pca_from_moments``, once, from the 8 D^2 bytes read back.  ``return_moments=True``: -> (reducer, {'n', 'colsum', 'center',
+        'gram'} as NumPy).  The same corpus gives the same reducer bit for bit, on every rank.
+        ValueError: an n_components that is no integer or lies outside 1 .. min(N, D), N < 2, an unknown field, 'embeddings2' without
+        a second input; RuntimeError on a CPU-device corpus (there is no CPU fallback)."""
+        from .pca import check_n_components, pca_from_moments
+        if field not in ('embeddings', 'embeddings2'):
+            raise ValueError(f"fit_pca: field is 'embeddings' or 'embeddings2', not {field!r}")
+        x = self.corpus if field == 'embeddings' else self.corpus2
+        if x is None:
+            raise ValueError("fit_pca: field='embeddings2' needs a corpus with a second input")
+        n, D = int(x.shape[0]), int(x.shape[1])
+        k = check_n_components(n_components, n, D, 'fit_pca')
+        if self.device.type != 'cuda':
+            raise RuntimeError('ResidentCorpus.fit_pca computes the moments on the GPU (there is no CPU fallback)')
+        from . import ops
+        with torch.cuda.device(self.device):
+            colsum = ops.pca_colsum(x).cpu().numpy()
+            center = (colsum / n).astype(np.float32)
+            gram = ops.pca_gram(x, torch.from_numpy(center).to(self.device)).cpu().numpy()
+        reducer = pca_from_moments(n, colsum, center, gram, k)
+        return (reducer, {'n': n, 'colsum': colsum, 'center': center, 'gram': gram}) if return_moments else reducer
+
+    def projected(self, reducer, reducer2=None):
+        """-> a ResidentCorpus whose ``corpus`` is ``reducer.transform(self.corpus)``: [total_rows, k] in the wire dtype (bf16: rounded
+        once); ``corpus2`` likewise under ``reducer2``, else as it is.  Targets, the row table, the host tables, segments and domains
+        are SHARED with this corpus; the index ring is fresh.  Every batch method reads the width from the matrix.
+        ValueError when a reducer was fitted on another width, or reducer2 is given without a second input."""
+        import copy
+        if reducer.n_features_in_ != int(self.corpus.shape[1]):
+            raise ValueError(f'projected: the reducer was fitted on width {reducer.n_features_in_}, the corpus has {int(self.corpus.shape[1])}')
+        if reducer2 is not None:
+            if self.corpus2 is None:
+                raise ValueError('projected: reducer2 needs a corpus with a second input')
+            if reducer2.n_features_in_ != int(self.corpus2.shape[1]):
+                raise ValueError(f'projected: reducer2 was fitted on width {reducer2.n_features_in_}, the second input has {int(self.corpus2.shape[1])}')
+        out = copy.copy(self)
+        out._ring, out._turn = None, 0
+        out.corpus = reducer.transform(self.corpus)
+        if reducer2 is not None:
+            out.corpus2 = reducer2.transform(self.corpus2)
+        return out
 
 
 class AugmentedCorpus:
