@@ -265,6 +265,42 @@ int mts_pca_project(void* stream, int in_dtype, int out_dtype, int rows, int D, 
                     const float* center,        /* device [D] */
                     const float* w,             /* device [k, D], row-major: the components */
                     void* y);                   /* device [rows, k] in out_dtype, out */
+/* SENTENCE POOLING OF FRAME-LEVEL FEATURES (frames.ResidentFrames, ResidentCorpus.with_frames; reference: extract_embeddings.py:644-667,
+ * the six pooled variants _mean, _max, _mean_std, _max_std, _last, _delta_gap of a sentence's frame-level encoder output), csrc/frame_pool.hip.
+ * frames is [total_frames, D], row-major, contiguous, MTS_F32 | MTS_BF16, any D >= 1 and any alignment its dtype has (16-byte accesses when
+ * D is a multiple of 4 / 8 elements and the base is 16-byte aligned, element accesses otherwise).  Sentence s is the rows frame_start[s] ..
+ * frame_start[s + 1] (int64 [n_sent + 1]); entries are clamped into 0 .. total_frames before an address is formed and row offsets are
+ * 64-bit.  Output row s starts at out + s * ld_out (elements) in out_dtype MTS_F32 | MTS_BF16 (bf16: ONE rounding of the fp32 result, to
+ * nearest even); ld_out may exceed the width of the block written and nothing outside the block is touched, so the block can be written
+ * into the right-hand columns of a wider matrix.  A sentence without frames writes 0.  Both run on the caller's stream, use no atomics, no
+ * workspace and no dependence between workgroups, write every element of the block exactly once and give the same bits for the same inputs.
+ * MTS_ERR_INVALID before any device work: a null pointer, an unknown dtype / statistic / mode, n_sent < 1, D < 1, total_frames < 0, ld_out
+ * smaller than the block written, nothing to compute (MTS_POOL_NONE without with_std).
+ *   mts_frame_pool   the reductions, one launch: the first statistic (MTS_POOL_MEAN | MTS_POOL_MAX | MTS_POOL_NONE: none) into columns
+ *                    [0, D) and, with_std = 1, the population standard deviation into the D columns behind it ([D, 2D); [0, D) after
+ *                    MTS_POOL_NONE).  Per sentence of n frames and per column, the element upcast to fp32 once, every operation fp32 and
+ *                    correctly rounded:  m = fl(fl(sum x) / n);  max exact;  std = fl(sqrt(fl(fl(sum fl(fl(x - m)^2)) / n))) -- the
+ *                    deviations about the COMPUTED mean m, as np.std.  Order of a sum: wave w of four adds rows w, w + 4, .. in ascending
+ *                    order into one chain, the four chains are added as ((p0 + p1) + p2) + p3.
+ *   mts_frame_edges  the gathers: MTS_EDGE_LAST is the sentence's last frame; MTS_EDGE_DELTA_GAP is the frame at row frame_start[s + 1] (the
+ *                    next sentence's first frame) minus the last frame, one fp32 subtraction, and the last frame itself where doc_last[s]
+ *                    != 0 (the last sentence of its document: upstream's IndexError branch) or s = n_sent - 1.  doc_last may be null for
+ *                    MTS_EDGE_LAST. */
+typedef enum { MTS_POOL_NONE = 0, MTS_POOL_MEAN = 1, MTS_POOL_MAX = 2 } mts_pool_stat;
+typedef enum { MTS_EDGE_LAST = 0, MTS_EDGE_DELTA_GAP = 1 } mts_edge_mode;
+int mts_frame_pool(void* stream, int in_dtype, int out_dtype, int n_sent, int D, int first, int with_std,
+                   const void* frames,          /* device [total_frames, D] in in_dtype */
+                   int64_t total_frames,
+                   const int64_t* frame_start,  /* device [n_sent + 1], ascending */
+                   void* out,                   /* device: row s at out + s * ld_out, D or 2 D columns written */
+                   int64_t ld_out);
+int mts_frame_edges(void* stream, int in_dtype, int out_dtype, int n_sent, int D, int mode,
+                    const void* frames,         /* device [total_frames, D] in in_dtype */
+                    int64_t total_frames,
+                    const int64_t* frame_start, /* device [n_sent + 1], ascending */
+                    const uint8_t* doc_last,    /* device [n_sent]: 1 on the last sentence of a document */
+                    void* out,                  /* device: row s at out + s * ld_out, D columns written */
+                    int64_t ld_out);
 
 /* ---------------------------------------------------------------------------------------------
  * LayerNorm family (biased variance, eps inside sqrt).

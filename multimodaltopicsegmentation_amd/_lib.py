@@ -36,6 +36,8 @@ lib = C.CDLL(LIB_PATH)
 F32, BF16 = 0, 1
 LOSS_CE, LOSS_BCE, LOSS_FOCAL = 0, 1, 2
 NT, NN, TN, TT = 0, 1, 2, 3
+POOL_NONE, POOL_MEAN, POOL_MAX = 0, 1, 2
+EDGE_LAST, EDGE_DELTA_GAP = 0, 1
 EPI_BIAS, EPI_RESIDUAL, EPI_GELU, EPI_COLSCALE, EPI_ACCUM, EPI_RELU = 1, 2, 4, 8, 16, 32
 
 _vp, _i, _f, _u, _sz = C.c_void_p, C.c_int, C.c_float, C.c_uint, C.c_size_t
@@ -132,6 +134,8 @@ SIGNATURES = {
     'mts_pca_colsum': (_i, [_vp, _i, _i, _i, _vp, _vp]),
     'mts_pca_gram': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     'mts_pca_project': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'mts_frame_pool': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, C.c_int64, _vp, _vp, C.c_int64]),
+    'mts_frame_edges': (_i, [_vp, _i, _i, _i, _i, _i, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64]),
 }
 
 _missing = []

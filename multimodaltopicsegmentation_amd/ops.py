@@ -309,6 +309,46 @@ def pca_project(x, center, w, y=None):
     return y
 
 
+def _frame_args(frames, frame_start, out, width):
+    """the checks the two frame entry points share -> (n_sent, D, ld_out); ``out`` is [n_sent, width] with unit column stride and any
+    row stride >= width (a column block of a wider matrix)"""
+    assert frames.dim() == 2 and frames.is_contiguous() and frames.is_cuda, 'a contiguous [total_frames, D] device matrix is expected'
+    assert frame_start.dtype == torch.int64 and frame_start.dim() == 1 and frame_start.is_contiguous() and frame_start.numel() >= 2
+    n_sent, D = frame_start.numel() - 1, int(frames.shape[1])
+    assert out.dim() == 2 and tuple(out.shape) == (n_sent, width * D) and (out.stride(1) == 1 or out.shape[1] == 1)
+    ld_out = int(out.stride(0)) if n_sent > 1 else max(int(out.stride(0)), width * D)
+    assert ld_out >= width * D
+    assert frames.device == frame_start.device == out.device
+    return n_sent, D, ld_out
+
+
+def frame_pool(frames, frame_start, out, first='mean', with_std=False):
+    """the pooled statistics of every sentence of a frame matrix (include/mts.h mts_frame_pool): frames fp32 / bf16 [total_frames, D],
+    sentence s = rows frame_start[s] .. frame_start[s + 1] (int64 [n_sent + 1], on the device).  ``first`` ('mean' | 'max' | None) goes
+    to out[:, :D], the population standard deviation (``with_std``) to the D columns behind it.  out: fp32 / bf16 [n_sent, D or 2 D],
+    unit column stride, any row stride (a column block of a wider matrix: the rest of it is not touched).  Every element of out is
+    written."""
+    code = {None: L.POOL_NONE, 'mean': L.POOL_MEAN, 'max': L.POOL_MAX}[first]
+    n_sent, D, ld_out = _frame_args(frames, frame_start, out, (first is not None) + bool(with_std))
+    check(lib.mts_frame_pool(stream_ptr(), dtype_code(frames.dtype), dtype_code(out.dtype), n_sent, D, code, int(bool(with_std)), ptr(frames),
+                             int(frames.shape[0]), ptr(frame_start), ptr(out), ld_out))
+    return out
+
+
+def frame_edges(frames, frame_start, doc_last, out, mode='last'):
+    """the two gathers of sentence pooling (include/mts.h mts_frame_edges): 'last' is every sentence's last frame, 'delta_gap' the next
+    sentence's first frame minus it, and the last frame itself where doc_last[s] (uint8 [n_sent], on the device; may be None for 'last')
+    marks the last sentence of a document.  out as in frame_pool, [n_sent, D]."""
+    code = {'last': L.EDGE_LAST, 'delta_gap': L.EDGE_DELTA_GAP}[mode]
+    n_sent, D, ld_out = _frame_args(frames, frame_start, out, 1)
+    assert doc_last is not None or mode == 'last'
+    if doc_last is not None:
+        assert doc_last.dtype == torch.uint8 and doc_last.is_contiguous() and doc_last.numel() == n_sent and doc_last.device == out.device
+    check(lib.mts_frame_edges(stream_ptr(), dtype_code(frames.dtype), dtype_code(out.dtype), n_sent, D, code, ptr(frames), int(frames.shape[0]),
+                              ptr(frame_start), ptr(doc_last), ptr(out), ld_out))
+    return out
+
+
 def embed_layernorm_fwd(x, pos, pos_offset, type0, gamma, beta, eps, y, pre, mean, rstd, row_src=None, x2=None):
     """row_src (int32 [n_rows], optional): packed batch -- output row r is sentence row_src[r] = b*L + i of x.
     x2 (fp32 [B, L, D2], optional): K-split input -- the row is x[b, i] | x2[b, i] and the concatenation is never materialised."""

@@ -27,7 +27,10 @@ at D = 1792, 238 MB in fp32, against 288 GB), so the fastest host collater is no
     compacts on the device, ``ops.gather_rows`` builds the tensors from its row table: two more integers per document in the per-call copy;
   * ``corpus.fit_pca(n_components)`` fits a ``pca.PcaReducer`` on the resident rows (the reference's ``--pca_reduce``; moments by
     ``ops.pca_colsum`` / ``ops.pca_gram``, csrc/pca.hip) and ``corpus.projected(reducer)`` is the corpus at width k (``ops.pca_project``):
-    every method above reads the width from the matrix and takes it as it is.
+    every method above reads the width from the matrix and takes it as it is;
+  * ``corpus.with_frames(frames, mode, field)`` takes an input from frame-level audio features pooled per sentence on the device
+    (``frames.ResidentFrames``, csrc/frame_pool.hip; the reference's six pooled variants): as the first input, as the second, or
+    early-fused behind the stored columns.
 
 For every tagger but ``SwitchBiLSTM(switch='dense')`` (see ``trainer.shard_batch``), ``corpus.batch(*item)`` on rank r holds the bits of
 ``shard_batch(collated global batch, r, world)``.  ``NativeTrainer.step`` takes these batches as they are.
@@ -490,6 +493,49 @@ class ResidentCorpus:
         out.corpus = reducer.transform(self.corpus)
         if reducer2 is not None:
             out.corpus2 = reducer2.transform(self.corpus2)
+        return out
+
+    # ---- sentence pooling of frame-level features ----------------------------------------------------------------------------
+    def with_frames(self, frames, mode, field='embeddings'):
+        """-> a ResidentCorpus that takes one input from ``frames`` (a ``frames.ResidentFrames``) pooled in ``mode`` (one of
+        ``frames.POOL_MODES``; the reference's _mean, _max, _mean_std, _max_std, _last, _delta_gap, extract_embeddings.py:644-667) by
+        ``frames.pool`` (csrc/frame_pool.hip), in this corpus' wire dtype:
+          * ``field='embeddings'``: the pooled matrix replaces the first input;
+          * ``field='embeddings2'``: it is the second input (a text-only corpus becomes a late-fusion corpus);
+          * ``field='append'``: early fusion -- a new [total_rows, D0 + W] first input whose left block is the stored one and whose right
+            block the kernel writes in place (its ld_out is the new width): no concatenated temporary.
+        Like ``projected``: targets, the row table, the host tables, segments and domains are SHARED with this corpus, the index ring is
+        fresh, and every batch method reads the width from the matrix.
+        ValueError: an unknown mode or field, frames on another device, documents or sentences per document that are not this corpus';
+        RuntimeError on a CPU-device corpus (there is no CPU fallback)."""
+        import copy
+        from .frames import pooled_width
+        W = pooled_width(mode, frames.D)
+        if field not in ('embeddings', 'embeddings2', 'append'):
+            raise ValueError(f"with_frames: field is 'embeddings', 'embeddings2' or 'append', not {field!r}")
+        if frames.n_docs != self.n_docs:
+            raise ValueError(f'with_frames: the frames hold {frames.n_docs} documents, the corpus {self.n_docs}')
+        bad = np.flatnonzero(frames.sentences != self.rows)
+        if bad.size:
+            d = int(bad[0])
+            raise ValueError(f'with_frames: document {d} has {int(self.rows[d])} sentences in the corpus but {int(frames.sentences[d])} in the frames')
+        if frames.device != self.device:
+            raise ValueError(f'with_frames: the frames are on {frames.device}, the corpus on {self.device}')
+        if self.device.type != 'cuda':
+            raise RuntimeError('ResidentCorpus.with_frames pools on the GPU (there is no CPU fallback)')
+        out = copy.copy(self)
+        out._ring, out._turn = None, 0
+        with torch.cuda.device(self.device):
+            if field == 'append':
+                D0 = int(self.corpus.shape[1])
+                wide = torch.empty((self.total_rows, D0 + W), dtype=self.wire, device=self.device)
+                wide[:, :D0].copy_(self.corpus)
+                frames.pool(mode, out=wide[:, D0:])
+                out.corpus = wide
+            elif field == 'embeddings':
+                out.corpus = frames.pool(mode, out_dtype=self.wire)
+            else:
+                out.corpus2 = frames.pool(mode, out_dtype=self.wire)
         return out
 
 
