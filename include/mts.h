@@ -598,6 +598,38 @@ int mts_tagger_loss(void* stream, int loss_kind, int B, int L, int Lt, int n_out
 /* tags_out: uint8 [B, L]; positions >= length are 0.  prob > threshold, strict; prob = sigmoid (n_out 1) or softmax[..., 1] (n_out 2..4). */
 int mts_greedy_decode(void* stream, int B, int L, int n_out, const float* scores, const int32_t* lengths,
                       float threshold, uint8_t* tags_out);
+/* PREDICTION PASS: SEGMENT TABLES AND A MINIMUM-LENGTH DECODE (predict.py; csrc/segment_decode.hip).  Replaces what a caller of the
+ * reference's predict.py does on the host after the forward -- tag lists per document, then a loop per list -- and adds a decode under a
+ * minimum segment length (an extension: upstream has none, and no claim about Pk is made for it).  scores fp32 [B, L, n_out], n_out 1..4;
+ * lengths int32 [B], NULL = every document has L sentences (clamped to 0..L).  For document b of n sentences, in ONE launch:
+ *   p_i = the probability of mts_greedy_decode, same bits;  prob[b, i] = p_i for i < n and 0 behind (prob may be NULL)
+ *   min_segment == 1:   tag_i = p_i > threshold, strict: bit for bit what mts_greedy_decode writes, at any threshold
+ *   min_segment = m >= 2, exact in integers:  P_i = rint((double) p_i * 2^32),  T = rint((double) threshold * 2^32) as int64, half to
+ *     even;  q_i = P_i - T.  The last sentence keeps the greedy rule, tag_{n-1} = p_{n-1} > threshold (it ends the document either
+ *     way).  Interior boundaries are eligible at t in [m-1, n-1-m] only, so the first and the last segment hold at least m sentences
+ *     too; n < 2m gives none.  With best(u) = 0 for u < m-1 and t ascending:
+ *         cand_t = q_t + best(t - m);   take_t = cand_t > best(t - 1), strict;   best(t) = max(best(t - 1), cand_t)
+ *     and the walk back from t = n-1-m: down to the largest u <= t with take_u, tag_u = 1, continue at t = u - m.  This maximises
+ *     sum_{t in S} (p_t - threshold) over the admissible boundary sets S (any two boundaries at least m apart), the minimum-expected-cost
+ *     decode whose m = 1 case is the threshold rule: for thresholds in [2^-8, 1) T is exact and q_t > 0 iff p_t > threshold.  The rule
+ *     is these integers, not a mapping onto threads: any parallelisation gives the same bits.  threshold must lie in [-1024, 1024].
+ *   tags[b, i] (uint8, may be NULL) = tag_i for i < n, 0 behind
+ *   seg_end[b, j] = the position BEHIND the j-th sentence with tag 1 (an exclusive end), ascending; with close_last != 0, n > 0 and
+ *     tag_{n-1} == 0 one more entry, n (the tail).  n_seg[b] = their number, NOT clipped to Smax (mts_mask_plan's rule); entries at
+ *     j >= min(n_seg[b], Smax) are -1.  n == 0 gives n_seg = 0.
+ * One workgroup per document; masks, prefix popcounts and a ring of the last m best() values in LDS.  Every element of every output is
+ * written exactly once by a plain vector store: no atomics, no workspace, no memset; the same bits on every call.
+ * MTS_ERR_INVALID before any device work: B < 0, L < 1, Smax < 1, n_out outside 1..4, with min_segment >= 2 a threshold outside
+ * [-1024, 1024] or NaN, and with B > 0 a null scores / seg_end / n_seg.  MTS_ERR_UNSUPPORTED: L > 65536, min_segment outside 1..1024.
+ * B == 0 returns MTS_OK without a launch. */
+int mts_segment_decode(void* stream, int B, int L, int n_out,
+                       const float* scores,         /* device fp32 [B, L, n_out] */
+                       const int32_t* lengths,      /* device [B] or NULL */
+                       float threshold, int min_segment, int close_last, int Smax,
+                       uint8_t* tags,               /* device [B, L] or NULL */
+                       float* prob,                 /* device [B, L] or NULL */
+                       int32_t* seg_end,            /* device [B, Smax] */
+                       int32_t* n_seg);             /* device [B] */
 /* DECISION-THRESHOLD SWEEP.  Replaces the host loop of models/lightning_model.py:435-553 (the disabled validation-epoch hook) over
  * compute_Pk / compute_window_diff / f1_score: for every document b and threshold j the six integers from which Pk, WindowDiff and
  * boundary-F1 follow exactly.  scores fp32 [B, L, n_out], n_out 1..4; targets fp32 [B, Lt], Lt >= L, 0 / 1 inside a document's length

@@ -100,6 +100,7 @@ SIGNATURES = {
     'mts_tagger_loss_workspace': (_sz, [_i, _i]),
     'mts_tagger_loss': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _sz, _vp, _i]),
     'mts_greedy_decode': (_i, [_vp, _i, _i, _i, _vp, _vp, _f, _vp]),
+    'mts_segment_decode': (_i, [_vp, _i, _i, _i, _vp, _vp, _f, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'mts_threshold_sweep': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp]),
     'mts_winpr_sweep': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _vp]),
     'mts_bootstrap_sums': (_i, [_vp, _i, _i, _i, _vp, C.c_uint64, _vp]),

@@ -2,7 +2,7 @@
 over the test split with per-document results, :414-427, the fold means, :497-520, and the 10 000-sample bootstrap that turns them into
 "mean +- 95 % half-width", :540-562 and compute_accuracy_metrics_sentence.py:63-260).
 
-    evaluate(trainer_or_model, corpus, batch_size=8, threshold=None)      -> per-document Pk / WD / F1 / WinPR, their means, the integers
+    evaluate(trainer_or_model, corpus, batch_size=8, threshold=None, min_segment=None) -> per-document Pk / WD / F1 / WinPR, their means, the integers
     bootstrap_ci(values, samples=10000, seed=0)                           -> mean, 2.5 / 97.5 percentiles of the resample means, half width
     paired_bootstrap(a, b, samples=10000, seed=0)                         -> the same for a - b, and the share of resamples on either side of 0
     cross_validate(make_trainer, folds, **fit_keywords)                   -> fit + evaluate per fold, fold means, report, pooled report
@@ -61,20 +61,43 @@ def _saturated(tags, L, device):
     return torch.from_numpy(h).to(device)
 
 
+def _constrained_logits(scores, lengths, threshold, min_segment):
+    """scores [B, L, n_out] -> the saturated fp32 [B, L, 1] logits of the constrained decode's tags, built on the device"""
+    scores = scores.detach().to(torch.float32).contiguous()
+    B, Lq = int(scores.shape[0]), int(scores.shape[1])
+    dev = scores.device
+    li = torch.as_tensor(lengths).to(device=dev, dtype=torch.int32).contiguous()
+    tags = torch.empty((B, Lq), dtype=torch.uint8, device=dev)
+    ops.segment_decode(scores, li, threshold, torch.empty((B, 1), dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+                       min_segment=min_segment, close_last=False, tags=tags)
+    return (tags.to(torch.float32) * (2 * SATURATED) - SATURATED).unsqueeze(-1)
+
+
 def evaluate(trainer_or_model, corpus, *, batch_size=8, threshold=None, end_boundary=False, winpr_k=10, zero_baseline=False,
-             return_scores=False):
+             return_scores=False, min_segment=None):
     """-> {'threshold', 'documents': int64 corpus indices ascending, 'per_document': {'Pk', 'WD', 'F1', 'b_precision', 'b_recall', 'b_f1'}
     float64 [n] each, 'mean': the same six keys -> float, 'counts': {'sweep': int64 [n, 6] = {pk_err, wd_err, windows, tp, fp, fn}, 'winpr':
     int64 [n, 3] = {TP, FP, FN}}}; the same values on every rank.  ``trainer_or_model``: a ``NativeTrainer`` (rank, world and process group
     are its) or a bare tagger / ``TextSegmenter`` (a single process).  ``return_scores=True`` adds 'scores': one fp32 array [length, n_out]
     per document THIS rank scored (``documents[rank::world]``), trimmed to the document's length -- the saturated logits for the Viterbi
     path and the baseline.  With segeval importable the six-integer sweep keeps host metrics (ThresholdSweep's rule): 'counts'['sweep'] is
-    None then."""
+    None then.  ``min_segment=m >= 2``: the hypothesis is the constrained decode of ``predict`` (``ops.segment_decode`` at the threshold,
+    segments of at least m sentences; an extension without an upstream counterpart): its tags become saturated logits on the device and
+    both sweeps run at 0.5; 'threshold' is the one the decode used, 'scores' the saturated logits.  None or 1 leaves the pass as it is."""
     model, rank, world, pg, merge = _unwrap(trainer_or_model)
     n_docs = len(corpus)
     if n_docs == 0:
         raise ValueError('evaluate: the corpus has no documents')
+    if not getattr(corpus, 'labelled', True):
+        raise ValueError('evaluate: the corpus is unlabelled (ResidentCorpus.from_documents); predict is the pass that needs no labels')
     viterbi = isinstance(model, BiRnnCrf) and model.decode == 'viterbi'
+    m = 1 if min_segment is None else int(min_segment)
+    if m < 1:
+        raise ValueError(f'evaluate: min_segment={min_segment}; a segment holds at least one sentence')
+    if m > 1 and viterbi:
+        raise ValueError("evaluate: min_segment > 1 needs probabilities; BiRnnCrf(decode='viterbi') has a path, not scores "
+                         "(decode='marginal' gives them)")
+    constrained = m > 1 and not zero_baseline
     if zero_baseline:
         reported, at = FALLBACK_THRESHOLD, 0.5
     elif viterbi:
@@ -87,6 +110,8 @@ def evaluate(trainer_or_model, corpus, *, batch_size=8, threshold=None, end_boun
             th = 0.5
         reported = at = float(th)
     invert = isinstance(model, SheikhBiLSTM) and not zero_baseline
+    if constrained:                                    # the decode takes the threshold (and SheikhBiLSTM's inversion); the sweeps see decisions
+        decode_at, at, invert = (1.0 - at if invert else at), 0.5, False
     six = ThresholdSweep(thresholds=[at], end_boundary=end_boundary, invert=invert, metric=None)
     win = ThresholdSweep(thresholds=[at], end_boundary=end_boundary, invert=invert, metric='scaiano', winpr_k=winpr_k)
     docs = list(range(rank, n_docs, world))
@@ -107,6 +132,8 @@ def evaluate(trainer_or_model, corpus, *, batch_size=8, threshold=None, end_boun
                     scores = _saturated(model(batch['src_tokens'], batch['src_lengths'])[1], batch['tgt_tokens'].shape[1], dev)
                 else:
                     scores = _forward(model, batch)
+                if constrained:
+                    scores = _constrained_logits(scores, batch['src_lengths'], decode_at, m)
                 six.add(scores, batch['tgt_tokens'], batch['src_lengths'], keys=idx)
                 win.add(scores, batch['tgt_tokens'], batch['src_lengths'], keys=idx)
                 if return_scores:

@@ -114,6 +114,9 @@ def fit(trainer, train, val=None, *, batch_size, max_epochs, search_threshold=Fa
     drawn anew every epoch); validation never masks.  The two views do not compose: both at once is a ValueError."""
     if augment is not None and mask_inner is not None:
         raise ValueError('fit: augment= and mask_inner= cannot be combined (the two corpus views do not compose)')
+    for name, c in (('training', train), ('validation', val)):
+        if c is not None and not getattr(c, 'labelled', True):
+            raise ValueError(f'fit: the {name} corpus is unlabelled (ResidentCorpus.from_documents); predict is the pass that needs no labels')
     model = trainer.model
     world = trainer.world
     rank = dist.get_rank(trainer.pg) if world > 1 else 0

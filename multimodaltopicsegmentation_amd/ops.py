@@ -691,6 +691,26 @@ def greedy_decode(scores, lengths, threshold, tags_out):
     check(lib.mts_greedy_decode(stream_ptr(), B, Lq, n_out, ptr(scores), ptr(lengths), float(threshold), ptr(tags_out)))
 
 
+def segment_decode(scores, lengths, threshold, seg_end, n_seg, min_segment=1, close_last=True, tags=None, prob=None):
+    """boundary tags, probabilities and the segment table of every document in one launch (include/mts.h mts_segment_decode): scores fp32
+    [B, L, n_out], lengths int32 [B] or None.  ``min_segment == 1``: tag = prob > threshold, greedy_decode's bits; ``>= 2``: the best
+    boundary set whose segments all hold at least that many sentences, exact in integers.  seg_end int32 [B, Smax]: the exclusive ends of
+    the segments in order (the tail's, the document's length, under ``close_last``), -1 behind; n_seg int32 [B]: their number, not
+    clipped to Smax; tags uint8 [B, L] and prob fp32 [B, L] are optional.  Every element of every output is written.
+    -> (seg_end, n_seg)"""
+    assert scores.dim() == 3 and scores.dtype == torch.float32 and scores.is_contiguous()
+    B, Lq, n_out = scores.shape
+    assert lengths is None or (lengths.dtype == torch.int32 and lengths.numel() == B and lengths.is_contiguous() and lengths.device == scores.device)
+    assert seg_end.dtype == torch.int32 and seg_end.dim() == 2 and seg_end.shape[0] == B and seg_end.is_contiguous()
+    assert n_seg.dtype == torch.int32 and n_seg.numel() == B and n_seg.is_contiguous()
+    assert tags is None or (tags.dtype == torch.uint8 and tags.numel() == B * Lq and tags.is_contiguous() and tags.device == scores.device)
+    assert prob is None or (prob.dtype == torch.float32 and prob.numel() == B * Lq and prob.is_contiguous() and prob.device == scores.device)
+    assert scores.device == seg_end.device == n_seg.device
+    check(lib.mts_segment_decode(stream_ptr(), B, Lq, n_out, ptr(scores), ptr(lengths), float(threshold), int(min_segment),
+                                 int(bool(close_last)), int(seg_end.shape[1]), ptr(tags), ptr(prob), ptr(seg_end), ptr(n_seg)))
+    return seg_end, n_seg
+
+
 def _sweep_operands(scores, targets, lengths, thresholds, counts_out, width):
     """the argument checks the two sweep kernels share -> (B, L, n_out, T)"""
     B, Lq, n_out = scores.shape

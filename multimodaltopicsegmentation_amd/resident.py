@@ -30,7 +30,10 @@ at D = 1792, 238 MB in fp32, against 288 GB), so the fastest host collater is no
     every method above reads the width from the matrix and takes it as it is;
   * ``corpus.with_frames(frames, mode, field)`` takes an input from frame-level audio features pooled per sentence on the device
     (``frames.ResidentFrames``, csrc/frame_pool.hip; the reference's six pooled variants): as the first input, as the second, or
-    early-fused behind the stored columns.
+    early-fused behind the stored columns;
+  * ``ResidentCorpus.from_documents(embeddings, device, names=)`` is an UNLABELLED corpus from a list of [sentences, D] matrices (what
+    ``load_dataset_for_inference`` returns): all-zero targets, ``labelled = False``, for ``predict.predict``; ``fit`` and ``evaluate``
+    refuse it.
 
 For every tagger but ``SwitchBiLSTM(switch='dense')`` (see ``trainer.shard_batch``), ``corpus.batch(*item)`` on rank r holds the bits of
 ``shard_batch(collated global batch, r, world)``.  ``NativeTrainer.step`` takes these batches as they are.
@@ -86,7 +89,43 @@ def _rows_2d(items, what):
     return out
 
 
+class _UnlabelledDocuments:
+    """what ``ResidentCorpus.__init__`` reads of a dataset, for a list of documents without labels (``from_documents``)"""
+    truncate, tv, minus, segments = False, 0, 1, False
+
+    def __init__(self, embeddings, embeddings2, domain):
+        self.embeddings = list(embeddings)
+        self.embeddings2 = list(embeddings2) if embeddings2 is not None else []
+        self.tgt_dataset = [torch.zeros(int(torch.as_tensor(e).shape[0]) if torch.as_tensor(e).dim() else 0) for e in self.embeddings]
+        self.da = domain is not None
+        self.domain = list(domain) if domain is not None else [None] * len(self.embeddings)
+        if len(self.domain) != len(self.embeddings):
+            raise ValueError(f'ResidentCorpus.from_documents: {len(self.embeddings)} documents but {len(self.domain)} domains')
+
+    def __len__(self):
+        return len(self.embeddings)
+
+
 class ResidentCorpus:
+    labelled = True                 # False for a corpus of ``from_documents``: fit and evaluate refuse it, predict takes either
+    names = None                    # the documents' file names (``from_documents(names=...)``)
+
+    @classmethod
+    def from_documents(cls, embeddings, device, wire_dtype='fp32', embeddings2=None, names=None, domain=None):
+        """-> an UNLABELLED corpus from a list of [sentences, D] matrices -- what ``datasets.load_dataset_for_inference`` returns next to
+        the file names (the reference's predict.py:293-300: AudioPortionDatasetInference over that list).  Targets are all zero, nothing
+        is truncated, ``names`` (the file names, or None) is kept as ``corpus.names`` and ``corpus.labelled`` is False.  ``batch``,
+        ``projected(reducer)`` and ``with_frames`` work on it as they are; ``fit`` and ``evaluate`` refuse it -- ``predict`` is the pass
+        that needs no labels.  ValueError: no documents, a document that is no matrix, widths that differ, names / domains / a second
+        input of another length."""
+        out = cls(_UnlabelledDocuments(embeddings, embeddings2, domain), device, wire_dtype=wire_dtype)
+        if names is not None:
+            names = list(names)
+            if len(names) != out.n_docs:
+                raise ValueError(f'ResidentCorpus.from_documents: {out.n_docs} documents but {len(names)} names')
+        out.names, out.labelled = names, False
+        return out
+
     def __init__(self, dataset, device, wire_dtype=None, segments=None):
         """dataset: an AudioPortionDataset; wire_dtype: 'fp32' | 'bf16' | None (the dataset's own); segments: add 'src_segments' to the
         batches (None: as the dataset does)."""

@@ -292,6 +292,11 @@ class NativeTrainer:
         from .evaluate import evaluate
         return evaluate(self, corpus, **kw)
 
+    def predict(self, corpus, **kw):
+        """The prediction pass over a ResidentCorpus, labelled or not: segment tables per document: predict.predict(self, ...)."""
+        from .predict import predict
+        return predict(self, corpus, **kw)
+
     def _check_same_length(self, Lq):
         """Shards of one global batch are collated together (same padded length).  Ranks that collate separately may differ:
         catch that once per distinct length instead of hanging in mismatched collectives."""
