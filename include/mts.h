@@ -771,6 +771,25 @@ int mts_crf_viterbi(void* stream, int B, int L, int C, const float* feats, const
  * the clamp drops a NaN) WITHOUT an error code.  The generic path (C != 4) works in the log domain and has no such limit. */
 int mts_crf_marginals(void* stream, int B, int L, int C, int cls, const float* feats, const int32_t* lengths,
                       const float* trans, float* scores, float* logz, float* workspace /* mts_crf_workspace(B, L, C) bytes */);
+/* The three entry points above on PACKED rows (the layout the transformer taggers train on: only the valid sentences, document after
+ * document).  Arguments of the sibling, then row0 int32 [B] (device) and n_rows:
+ *   feats / dfeats fp32 [n_rows, C]; document b owns rows row0[b] .. row0[b] + len_b - 1 (len_b: lengths[b] clamped to 0..L; lengths
+ *   must be given with row0); tags stays [B, Lt] and the workspace mts_crf_workspace(B, L, C) bytes (alphas are kept per document);
+ *   mts_crf_marginals_packed: scores fp32 [n_rows] (one logit per packed row, nothing behind them); logz [B];
+ *   mts_crf_viterbi_packed: paths stays int32 [B, L] with -1 past the length; bp_ws int32 [n_rows, C].
+ * The same kernels and the same arithmetic at other addresses: for rows that hold the same emissions the results are bitwise those of
+ * the padded entry points, and row0 == NULL IS the padded layout (n_rows is then only checked for its sign).  mts_crf_nll_packed scales
+ * the n_rows * C elements of dfeats by 1 / B and writes nothing behind them; rows of dfeats / scores that no document owns keep what
+ * they held (dfeats: times 1 / B).  A document whose rows would leave [0, n_rows) forms no address and contributes nothing: loss and
+ * gradients 0 (B still divides), best_score 0 and a path of -1, logz 0, no score written.  MTS_ERR_INVALID before any launch: a null
+ * operand, n_rows < 0, C outside 3..8, row0 without lengths.  No atomics; bitwise reproducible from launch to launch. */
+int mts_crf_nll_packed(void* stream, int B, int L, int C, const float* feats, const float* tags, int Lt,
+                       const int32_t* lengths, const float* trans, float* loss_out, float* dfeats, float* dtrans,
+                       float* workspace, const int32_t* row0, int n_rows);
+int mts_crf_viterbi_packed(void* stream, int B, int L, int C, const float* feats, const int32_t* lengths,
+                           const float* trans, float* best_score, int32_t* paths, int32_t* bp_ws, const int32_t* row0, int n_rows);
+int mts_crf_marginals_packed(void* stream, int B, int L, int C, int cls, const float* feats, const int32_t* lengths,
+                             const float* trans, float* scores, float* logz, float* workspace, const int32_t* row0, int n_rows);
 
 /* ---------------------------------------------------------------------------------------------
  * Optimizer step over a flat fp32 parameter buffer.

@@ -11,6 +11,7 @@ from .prefetch import DevicePrefetcher  # noqa: F401
 from .resident import AugmentedCorpus, DocumentShardSampler, MaskedCorpus, ResidentCorpus  # noqa: F401
 from .rnn_taggers import BiLSTM, BiLSTMLateFusion, BiRnnCrf, SheikhBiLSTM, SwitchBiLSTM  # noqa: F401
 from .t5_taggers import RecurrentLongT5  # noqa: F401
+from .crf_taggers import TransformerCRF  # noqa: F401
 from .taggers import RestrictedTransformerEncoderLayer, Transformer_segmenter  # noqa: F401
 from .threshold_search import DEFAULT_THRESHOLDS, ThresholdSweep  # noqa: F401
 from .fit import fit  # noqa: F401
@@ -19,7 +20,7 @@ from .predict import Prediction, predict, segment_audio  # noqa: F401
 from .pca import PcaReducer, pca_from_moments, project_folds  # noqa: F401
 from .frames import POOL_MODES, ResidentFrames, load_frames  # noqa: F401
 
-__all__ = ['TextSegmenter', 'Transformer_segmenter', 'BiLSTM', 'BiLSTMLateFusion', 'BiRnnCrf', 'RecurrentLongT5', 'SheikhBiLSTM', 'SwitchBiLSTM', 'AudioPortionDataset',
+__all__ = ['TextSegmenter', 'Transformer_segmenter', 'BiLSTM', 'BiLSTMLateFusion', 'BiRnnCrf', 'TransformerCRF', 'RecurrentLongT5', 'SheikhBiLSTM', 'SwitchBiLSTM', 'AudioPortionDataset',
            'AudioPortionDatasetInference', 'RestrictedTransformerEncoderLayer', 'DevicePrefetcher', 'ThresholdSweep', 'DEFAULT_THRESHOLDS', 'ResidentCorpus',
            'DocumentShardSampler', 'AugmentedCorpus', 'MaskedCorpus', 'fit', 'evaluate', 'bootstrap_ci', 'paired_bootstrap', 'cross_validate', 'Prediction', 'predict', 'segment_audio', 'PcaReducer',
            'pca_from_moments', 'project_folds', 'POOL_MODES', 'ResidentFrames', 'load_frames']

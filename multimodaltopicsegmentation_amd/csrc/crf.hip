@@ -8,6 +8,18 @@
 #define CRF_MAXC 8
 #define CRF_IMPOSSIBLE (-1e4f)
 
+// Row addressing shared by every kernel below.  row0 == NULL: the padded layout, document b owns rows b * L .. b * L + L - 1 of feats /
+// dfeats / scores / bp_ws.  row0 != NULL: PACKED rows (the transformer taggers' training layout, taggers.py _pack_plan): the buffers hold
+// n_rows rows and document b owns rows row0[b] .. row0[b] + n - 1 (n: its clamped length); nothing is written past them.  A document
+// whose rows would leave [0, n_rows) forms no address: crf_row_base returns false and the caller writes the document's neutral outputs
+// (the rule of switch_head.hip's maps).  The recursions are the same arithmetic at other addresses.
+__device__ __forceinline__ bool crf_row_base(const int32_t* __restrict__ row0, int n_rows, int b, int L, int n, size_t& base) {
+  if (!row0) { base = (size_t)b * L; return true; }
+  const int r0 = row0[b];
+  base = (size_t)max(r0, 0);
+  return r0 >= 0 && r0 <= n_rows - n;
+}
+
 __device__ __forceinline__ float lse_arr(const float* v, int n) {
   float m = v[0];
   for (int i = 1; i < n; ++i) m = fmaxf(m, v[i]);
@@ -47,17 +59,26 @@ __device__ __forceinline__ float quad_max(float v) { return fmaxf(fmaxf(quad_bca
 
 __global__ __launch_bounds__(64) void crf_nll4_kernel(int B, int L, const float* __restrict__ feats, const float* __restrict__ tags, int Lt,
                                                       const int32_t* __restrict__ lengths, const float* __restrict__ trans,
-                                                      float* __restrict__ dfeats, float* __restrict__ alphas, float* __restrict__ part) {
+                                                      float* __restrict__ dfeats, float* __restrict__ alphas, float* __restrict__ part,
+                                                      const int32_t* __restrict__ row0, int n_rows) {
   constexpr int C = 4, start = 2, stop = 3;
   const int i = threadIdx.x & 3;
   const int b = blockIdx.x * 16 + (threadIdx.x >> 2);
   if (b >= B) return;                                   // whole quads leave together
   const int n = lengths ? max(min(lengths[b], L), 0) : L;
+  size_t rb;
+  if (!crf_row_base(row0, n_rows, b, L, n, rb)) {       // (packed) rows out of range: no loss, no gradient, no address
+    float* pz = part + (size_t)b * (C * C + 1);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) pz[i * C + j] = 0.f;
+    if (i == 0) pz[C * C] = 0.f;
+    return;
+  }
   float Er[4], Ec[4];                                   // exp of my row (to me from j) and my column (from me to j) of the transition table
 #pragma unroll
   for (int j = 0; j < 4; ++j) { Er[j] = expf(trans[i * C + j]); Ec[j] = expf(trans[j * C + i]); }
   const float Estop = expf(trans[stop * C + i]);
-  const float* f = feats + (size_t)b * L * C;
+  const float* f = feats + rb * C;
   float* al = alphas + (size_t)b * (L + 1) * C;
   const float* tg = tags + (size_t)b * Lt;
   float p = (i == start) ? 1.f : 0.f;
@@ -98,7 +119,7 @@ __global__ __launch_bounds__(64) void crf_nll4_kernel(int B, int L, const float*
   float dT[4] = {0.f, 0.f, 0.f, 0.f};
   float bh = Estop / zn;                                 // bhat_n(i)
   const float dstop = p * bh;                            // P(last tag = i): row `stop`, column i
-  float* df = dfeats + (size_t)b * L * C;
+  float* df = dfeats + rb * C;
   // operands of step t: emission row, p_t and p_{t+1}, the gold tags -- requested two steps ahead
   float f0 = n > 0 ? f[(n - 1) * C + i] : 0.f, f1 = n > 1 ? f[(n - 2) * C + i] : 0.f;
   float a0 = n > 0 ? al[(n - 1) * C + i] : 0.f, a1 = n > 1 ? al[(n - 2) * C + i] : 0.f;
@@ -125,7 +146,8 @@ __global__ __launch_bounds__(64) void crf_nll4_kernel(int B, int L, const float*
     bh = fminf(((Ec[0] * quad_bcast<0>(w) + Ec[1] * quad_bcast<1>(w)) + Ec[2] * quad_bcast<2>(w)) + Ec[3] * quad_bcast<3>(w), 1e30f);
     pnext = pt;
   }
-  for (int t = n; t < L; ++t) df[t * C + i] = 0.f;
+  if (!row0)
+    for (int t = n; t < L; ++t) df[t * C + i] = 0.f;
   const float ds0 = quad_bcast<0>(dstop), ds1 = quad_bcast<1>(dstop), ds2 = quad_bcast<2>(dstop), ds3 = quad_bcast<3>(dstop);
   if (i == stop) {
     dT[0] += ds0; dT[1] += ds1; dT[2] += ds2; dT[3] += ds3;
@@ -141,17 +163,25 @@ __global__ __launch_bounds__(64) void crf_nll4_kernel(int B, int L, const float*
 // document (predict.py: one document per call) needed 156 KB for its block, and the call fell back to the generic kernel below: one lane, four
 // dependent global stores per step, 5.7 ms per document.
 __global__ __launch_bounds__(64) void crf_viterbi4_kernel(int B, int L, const float* __restrict__ feats, const int32_t* __restrict__ lengths,
-                                                          const float* __restrict__ trans, float* __restrict__ best_score, int32_t* __restrict__ paths) {
+                                                          const float* __restrict__ trans, float* __restrict__ best_score, int32_t* __restrict__ paths,
+                                                          const int32_t* __restrict__ row0, int n_rows) {
   extern __shared__ unsigned char bp_lds[];            // [16 documents][L]
   constexpr int C = 4, start = 2, stop = 3;
   const int i = threadIdx.x & 3, q = threadIdx.x >> 2;
   const int b = blockIdx.x * 16 + q;
   if (b >= B) return;
   const int n = lengths ? max(min(lengths[b], L), 0) : L;
+  size_t rb;
+  if (!crf_row_base(row0, n_rows, b, L, n, rb)) {       // (packed) rows out of range: an empty path with score 0
+    int32_t* pe = paths + (size_t)b * L;
+    for (int t = i; t < L; t += 4) pe[t] = -1;
+    if (i == 0) best_score[b] = 0.f;
+    return;
+  }
   float Tr[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) Tr[j] = trans[i * C + j];
-  const float* f = feats + (size_t)b * L * C;
+  const float* f = feats + rb * C;
   unsigned char* bp = bp_lds + (size_t)q * L;
   float m = (i == start) ? 0.f : CRF_IMPOSSIBLE;
   // emission rows four steps ahead of the step that needs them: the row is the only memory operand of a step, and a load issued one step
@@ -197,15 +227,21 @@ __global__ __launch_bounds__(64) void crf_viterbi4_kernel(int B, int L, const fl
 __global__ __launch_bounds__(64) void crf_nll_kernel(int B, int L, int C, const float* __restrict__ feats, const float* __restrict__ tags, int Lt,
                                                      const int32_t* __restrict__ lengths, const float* __restrict__ trans,
                                                      float* __restrict__ dfeats, float* __restrict__ alphas /*[B][L+1][C]*/,
-                                                     float* __restrict__ part /*[B][C*C + 1]*/) {
+                                                     float* __restrict__ part /*[B][C*C + 1]*/, const int32_t* __restrict__ row0, int n_rows) {
   const int b = blockIdx.x * 64 + threadIdx.x;
   if (b >= B) return;
   const int start = C - 2, stop = C - 1;
   const int n = lengths ? max(min(lengths[b], L), 0) : L;
+  size_t rb;
+  if (!crf_row_base(row0, n_rows, b, L, n, rb)) {
+    float* pz = part + (size_t)b * (C * C + 1);
+    for (int e = 0; e <= C * C; ++e) pz[e] = 0.f;
+    return;
+  }
   float T[CRF_MAXC][CRF_MAXC];
   for (int i = 0; i < C; ++i)
     for (int j = 0; j < C; ++j) T[i][j] = trans[i * C + j];
-  const float* f = feats + (size_t)b * L * C;
+  const float* f = feats + rb * C;
   float* al = alphas + (size_t)b * (L + 1) * C;
   float a[CRF_MAXC], tmp[CRF_MAXC];
   for (int i = 0; i < C; ++i) { a[i] = (i == start) ? 0.f : CRF_IMPOSSIBLE; al[i] = a[i]; }
@@ -242,7 +278,7 @@ __global__ __launch_bounds__(64) void crf_nll_kernel(int B, int L, int C, const 
     beta[i] = T[stop][i];
     dT[stop][i] += expf(a[i] + T[stop][i] - logZ);             // P(last tag = i)
   }
-  float* df = dfeats + (size_t)b * L * C;
+  float* df = dfeats + rb * C;
   for (int t = n - 1; t >= 0; --t) {
     const float* ap = al + t * C;                                // alpha before step t
     float nb[CRF_MAXC];
@@ -263,8 +299,9 @@ __global__ __launch_bounds__(64) void crf_nll_kernel(int B, int L, int C, const 
     }
     for (int i = 0; i < C; ++i) { df[t * C + i] = marg[i]; beta[i] = nb[i]; }
   }
-  for (int t = n; t < L; ++t)
-    for (int i = 0; i < C; ++i) df[t * C + i] = 0.f;
+  if (!row0)
+    for (int t = n; t < L; ++t)
+      for (int i = 0; i < C; ++i) df[t * C + i] = 0.f;
   // subtract the gold path's one-hot counts
   prev = start;
   for (int t = 0; t < n; ++t) {
@@ -278,8 +315,8 @@ __global__ __launch_bounds__(64) void crf_nll_kernel(int B, int L, int C, const 
     for (int j = 0; j < C; ++j) pp[i * C + j] = dT[i][j];
 }
 
-// mean over documents; scales dfeats by 1/B
-__global__ __launch_bounds__(256) void crf_finish_kernel(int B, int L, int C, const float* __restrict__ part, float* __restrict__ loss_out,
+// mean over documents; scales the n elements of dfeats (B * L * C padded, n_rows * C packed) by 1/B
+__global__ __launch_bounds__(256) void crf_finish_kernel(int B, int C, size_t n, const float* __restrict__ part, float* __restrict__ loss_out,
                                                          float* __restrict__ dfeats, float* __restrict__ dtrans) {
   const float inv = 1.f / (float)B;
   if (blockIdx.x == 0) {
@@ -292,7 +329,6 @@ __global__ __launch_bounds__(256) void crf_finish_kernel(int B, int L, int C, co
     }
   }
   if (dfeats) {
-    const size_t n = (size_t)B * L * C;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) dfeats[i] *= inv;
   }
 }
@@ -300,16 +336,23 @@ __global__ __launch_bounds__(256) void crf_finish_kernel(int B, int L, int C, co
 // Viterbi (CRF.py:172-216): first-max tie break as torch.max(dim=-1)
 __global__ __launch_bounds__(64) void crf_viterbi_kernel(int B, int L, int C, const float* __restrict__ feats, const int32_t* __restrict__ lengths,
                                                          const float* __restrict__ trans, float* __restrict__ best_score, int32_t* __restrict__ paths,
-                                                         int32_t* __restrict__ bps) {
+                                                         int32_t* __restrict__ bps, const int32_t* __restrict__ row0, int n_rows) {
   const int b = blockIdx.x * 64 + threadIdx.x;
   if (b >= B) return;
   const int start = C - 2, stop = C - 1;
   const int n = lengths ? max(min(lengths[b], L), 0) : L;
+  size_t rb;
+  if (!crf_row_base(row0, n_rows, b, L, n, rb)) {
+    int32_t* pe = paths + (size_t)b * L;
+    for (int t = 0; t < L; ++t) pe[t] = -1;
+    best_score[b] = 0.f;
+    return;
+  }
   float T[CRF_MAXC][CRF_MAXC];
   for (int i = 0; i < C; ++i)
     for (int j = 0; j < C; ++j) T[i][j] = trans[i * C + j];
-  const float* f = feats + (size_t)b * L * C;
-  int32_t* bp = bps + (size_t)b * L * C;
+  const float* f = feats + rb * C;
+  int32_t* bp = bps + rb * C;
   float m[CRF_MAXC];
   for (int i = 0; i < C; ++i) m[i] = (i == start) ? 0.f : CRF_IMPOSSIBLE;
   for (int t = 0; t < n; ++t) {
@@ -345,19 +388,51 @@ extern "C" size_t mts_crf_workspace(int B, int L, int C) {
   return ((size_t)B * (L + 1) * C + (size_t)B * (C * C + 1)) * sizeof(float);
 }
 
+// The launches of mts_crf_nll / mts_crf_nll_packed (row0 == NULL: the padded layout; arguments validated by the callers)
+static int crf_nll_launch(hipStream_t st, int B, int L, int C, const float* feats, const float* tags, int Lt, const int32_t* lengths, const float* trans,
+                          float* loss_out, float* dfeats, float* dtrans, float* workspace, const int32_t* row0, int n_rows, const char* who) {
+  float* alphas = workspace;
+  float* part = workspace + (size_t)B * (L + 1) * C;
+  if (C == 4)
+    hipLaunchKernelGGL(crf_nll4_kernel, dim3(ceil_div(B, 16)), dim3(64), 0, st, B, L, feats, tags, Lt, lengths, trans, dfeats, alphas, part, row0, n_rows);
+  else
+    hipLaunchKernelGGL(crf_nll_kernel, dim3(ceil_div(B, 64)), dim3(64), 0, st, B, L, C, feats, tags, Lt, lengths, trans, dfeats, alphas, part, row0, n_rows);
+  const size_t n = row0 ? (size_t)n_rows * C : (size_t)B * L * C;
+  const int blocks = dfeats ? (int)std::max<size_t>(1, std::min<size_t>(256, (n + 255) / 256)) : 1;
+  hipLaunchKernelGGL(crf_finish_kernel, dim3(blocks), dim3(256), 0, st, B, C, n, (const float*)part, loss_out, dfeats, dtrans);
+  MTS_LAUNCH_CHECK(who);
+  return MTS_OK;
+}
+
 extern "C" int mts_crf_nll(void* stream, int B, int L, int C, const float* feats, const float* tags, int Lt, const int32_t* lengths,
                            const float* trans, float* loss_out, float* dfeats, float* dtrans, float* workspace) {
   MTS_CHECK_ARG(B > 0 && L > 0 && C >= 3 && C <= CRF_MAXC && Lt >= L, "mts_crf_nll: bad shape (C must be in 3..8)");
   MTS_CHECK_ARG(feats && tags && trans && loss_out && workspace, "mts_crf_nll: null pointer");
   MTS_CHECK_ARG(!dtrans || dfeats, "mts_crf_nll: dtrans requires dfeats");
-  hipStream_t st = (hipStream_t)stream;
-  float* alphas = workspace;
-  float* part = workspace + (size_t)B * (L + 1) * C;
-  if (C == 4) hipLaunchKernelGGL(crf_nll4_kernel, dim3(ceil_div(B, 16)), dim3(64), 0, st, B, L, feats, tags, Lt, lengths, trans, dfeats, alphas, part);
-  else hipLaunchKernelGGL(crf_nll_kernel, dim3(ceil_div(B, 64)), dim3(64), 0, st, B, L, C, feats, tags, Lt, lengths, trans, dfeats, alphas, part);
-  const int blocks = dfeats ? std::min(256, ceil_div(B * L * C, 256)) : 1;
-  hipLaunchKernelGGL(crf_finish_kernel, dim3(blocks), dim3(256), 0, st, B, L, C, (const float*)part, loss_out, dfeats, dtrans);
-  MTS_LAUNCH_CHECK("mts_crf_nll");
+  return crf_nll_launch((hipStream_t)stream, B, L, C, feats, tags, Lt, lengths, trans, loss_out, dfeats, dtrans, workspace, nullptr, 0, "mts_crf_nll");
+}
+
+extern "C" int mts_crf_nll_packed(void* stream, int B, int L, int C, const float* feats, const float* tags, int Lt, const int32_t* lengths,
+                                  const float* trans, float* loss_out, float* dfeats, float* dtrans, float* workspace, const int32_t* row0,
+                                  int n_rows) {
+  MTS_CHECK_ARG(B > 0 && L > 0 && C >= 3 && C <= CRF_MAXC && Lt >= L && n_rows >= 0, "mts_crf_nll_packed: bad shape (C must be in 3..8, n_rows >= 0)");
+  MTS_CHECK_ARG(feats && tags && trans && loss_out && workspace, "mts_crf_nll_packed: null pointer");
+  MTS_CHECK_ARG(!dtrans || dfeats, "mts_crf_nll_packed: dtrans requires dfeats");
+  MTS_CHECK_ARG(!row0 || lengths, "mts_crf_nll_packed: packed rows need the lengths");
+  return crf_nll_launch((hipStream_t)stream, B, L, C, feats, tags, Lt, lengths, trans, loss_out, dfeats, dtrans, workspace, row0, n_rows,
+                        "mts_crf_nll_packed");
+}
+
+static int crf_viterbi_launch(hipStream_t st, int B, int L, int C, const float* feats, const int32_t* lengths, const float* trans, float* best_score,
+                              int32_t* paths, int32_t* bp_ws, const int32_t* row0, int n_rows, const char* who) {
+  const size_t bp_bytes = (size_t)16 * L;                   // one byte per document and step (four 2-bit back-pointers)
+  bool quad = C == 4 && bp_bytes <= 160 * 1024;
+  if (quad && mts_dyn_lds(crf_viterbi4_kernel, bp_bytes, who) != MTS_OK) quad = false;
+  if (quad)
+    hipLaunchKernelGGL(crf_viterbi4_kernel, dim3(ceil_div(B, 16)), dim3(64), bp_bytes, st, B, L, feats, lengths, trans, best_score, paths, row0, n_rows);
+  else
+    hipLaunchKernelGGL(crf_viterbi_kernel, dim3(ceil_div(B, 64)), dim3(64), 0, st, B, L, C, feats, lengths, trans, best_score, paths, bp_ws, row0, n_rows);
+  MTS_LAUNCH_CHECK(who);
   return MTS_OK;
 }
 
@@ -365,16 +440,15 @@ extern "C" int mts_crf_viterbi(void* stream, int B, int L, int C, const float* f
                                float* best_score, int32_t* paths, int32_t* bp_ws) {
   MTS_CHECK_ARG(B > 0 && L > 0 && C >= 3 && C <= CRF_MAXC, "mts_crf_viterbi: bad shape (C must be in 3..8)");
   MTS_CHECK_ARG(feats && trans && best_score && paths && bp_ws, "mts_crf_viterbi: null pointer");
-  const size_t bp_bytes = (size_t)16 * L;                   // one byte per document and step (four 2-bit back-pointers)
-  bool quad = C == 4 && bp_bytes <= 160 * 1024;
-  if (quad && mts_dyn_lds(crf_viterbi4_kernel, bp_bytes, "mts_crf_viterbi") != MTS_OK) quad = false;
-  if (quad)
-    hipLaunchKernelGGL(crf_viterbi4_kernel, dim3(ceil_div(B, 16)), dim3(64), bp_bytes, (hipStream_t)stream, B, L, feats, lengths, trans, best_score,
-                       paths);
-  else
-    hipLaunchKernelGGL(crf_viterbi_kernel, dim3(ceil_div(B, 64)), dim3(64), 0, (hipStream_t)stream, B, L, C, feats, lengths, trans, best_score, paths, bp_ws);
-  MTS_LAUNCH_CHECK("mts_crf_viterbi");
-  return MTS_OK;
+  return crf_viterbi_launch((hipStream_t)stream, B, L, C, feats, lengths, trans, best_score, paths, bp_ws, nullptr, 0, "mts_crf_viterbi");
+}
+
+extern "C" int mts_crf_viterbi_packed(void* stream, int B, int L, int C, const float* feats, const int32_t* lengths, const float* trans,
+                                      float* best_score, int32_t* paths, int32_t* bp_ws, const int32_t* row0, int n_rows) {
+  MTS_CHECK_ARG(B > 0 && L > 0 && C >= 3 && C <= CRF_MAXC && n_rows >= 0, "mts_crf_viterbi_packed: bad shape (C must be in 3..8, n_rows >= 0)");
+  MTS_CHECK_ARG(feats && trans && best_score && paths && bp_ws, "mts_crf_viterbi_packed: null pointer");
+  MTS_CHECK_ARG(!row0 || lengths, "mts_crf_viterbi_packed: packed rows need the lengths");
+  return crf_viterbi_launch((hipStream_t)stream, B, L, C, feats, lengths, trans, best_score, paths, bp_ws, row0, n_rows, "mts_crf_viterbi_packed");
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -390,19 +464,24 @@ extern "C" int mts_crf_viterbi(void* stream, int B, int L, int C, const float* f
 // shifted by its largest entry among the tags that carry probability, so a document of length 0 gives log Z = T[stop][start] exactly.
 __global__ __launch_bounds__(64) void crf_marg4_kernel(int B, int L, int cls, const float* __restrict__ feats, const int32_t* __restrict__ lengths,
                                                        const float* __restrict__ trans, float* __restrict__ scores, float* __restrict__ logz,
-                                                       float* __restrict__ alphas) {
+                                                       float* __restrict__ alphas, const int32_t* __restrict__ row0, int n_rows) {
   constexpr int C = 4, start = 2, stop = 3;
   const int i = threadIdx.x & 3;
   const int b = blockIdx.x * 16 + (threadIdx.x >> 2);
   if (b >= B) return;                                   // whole quads leave together
   const int n = lengths ? max(min(lengths[b], L), 0) : L;
+  size_t rb;
+  if (!crf_row_base(row0, n_rows, b, L, n, rb)) {       // (packed) rows out of range: no score is written
+    if (logz && i == 0) logz[b] = 0.f;
+    return;
+  }
   float Er[4], Ec[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) { Er[j] = expf(trans[i * C + j]); Ec[j] = expf(trans[j * C + i]); }
   const float tstop = trans[stop * C + i];
-  const float* f = feats + (size_t)b * L * C;
+  const float* f = feats + rb * C;
   float* al = alphas + (size_t)b * (L + 1) * C;
-  float* sc = scores + (size_t)b * L;
+  float* sc = scores + rb;
   float p = (i == start) ? 1.f : 0.f;
   al[i] = p;
   float logscale = 0.f;
@@ -449,24 +528,30 @@ __global__ __launch_bounds__(64) void crf_marg4_kernel(int B, int L, int cls, co
     bh = fminf(((Ec[0] * quad_bcast<0>(w) + Ec[1] * quad_bcast<1>(w)) + Ec[2] * quad_bcast<2>(w)) + Ec[3] * quad_bcast<3>(w), 1e30f);
     pnext = pt;
   }
-  for (int t = n + i; t < L; t += 4) sc[t] = 0.f;
+  if (!row0)
+    for (int t = n + i; t < L; t += 4) sc[t] = 0.f;
 }
 
 // generic C (3..8): one thread per document in the log domain, as crf_nll_kernel.  The logit is a difference of alpha + beta sums of one
 // step, so the rounding alpha and beta have in common cancels without a normalisation by log Z.
 __global__ __launch_bounds__(64) void crf_marg_kernel(int B, int L, int C, int cls, const float* __restrict__ feats, const int32_t* __restrict__ lengths,
                                                       const float* __restrict__ trans, float* __restrict__ scores, float* __restrict__ logz,
-                                                      float* __restrict__ alphas /*[B][L+1][C]*/) {
+                                                      float* __restrict__ alphas /*[B][L+1][C]*/, const int32_t* __restrict__ row0, int n_rows) {
   const int b = blockIdx.x * 64 + threadIdx.x;
   if (b >= B) return;
   const int start = C - 2, stop = C - 1;
   const int n = lengths ? max(min(lengths[b], L), 0) : L;
+  size_t rb;
+  if (!crf_row_base(row0, n_rows, b, L, n, rb)) {
+    if (logz) logz[b] = 0.f;
+    return;
+  }
   float T[CRF_MAXC][CRF_MAXC];
   for (int i = 0; i < C; ++i)
     for (int j = 0; j < C; ++j) T[i][j] = trans[i * C + j];
-  const float* f = feats + (size_t)b * L * C;
+  const float* f = feats + rb * C;
   float* al = alphas + (size_t)b * (L + 1) * C;
-  float* sc = scores + (size_t)b * L;
+  float* sc = scores + rb;
   float a[CRF_MAXC], tmp[CRF_MAXC];
   for (int i = 0; i < C; ++i) { a[i] = (i == start) ? 0.f : CRF_IMPOSSIBLE; al[i] = a[i]; }
   for (int t = 0; t < n; ++t) {
@@ -497,7 +582,16 @@ __global__ __launch_bounds__(64) void crf_marg_kernel(int B, int L, int C, int c
     }
     for (int i = 0; i < C; ++i) beta[i] = nb[i];
   }
-  for (int t = n; t < L; ++t) sc[t] = 0.f;
+  if (!row0)
+    for (int t = n; t < L; ++t) sc[t] = 0.f;
+}
+
+static int crf_marginals_launch(hipStream_t st, int B, int L, int C, int cls, const float* feats, const int32_t* lengths, const float* trans,
+                                float* scores, float* logz, float* workspace, const int32_t* row0, int n_rows, const char* who) {
+  if (C == 4) hipLaunchKernelGGL(crf_marg4_kernel, dim3(ceil_div(B, 16)), dim3(64), 0, st, B, L, cls, feats, lengths, trans, scores, logz, workspace, row0, n_rows);
+  else hipLaunchKernelGGL(crf_marg_kernel, dim3(ceil_div(B, 64)), dim3(64), 0, st, B, L, C, cls, feats, lengths, trans, scores, logz, workspace, row0, n_rows);
+  MTS_LAUNCH_CHECK(who);
+  return MTS_OK;
 }
 
 extern "C" int mts_crf_marginals(void* stream, int B, int L, int C, int cls, const float* feats, const int32_t* lengths, const float* trans,
@@ -505,9 +599,14 @@ extern "C" int mts_crf_marginals(void* stream, int B, int L, int C, int cls, con
   MTS_CHECK_ARG(B > 0 && L > 0 && C >= 3 && C <= CRF_MAXC, "mts_crf_marginals: bad shape (C must be in 3..8)");
   MTS_CHECK_ARG(cls >= 0 && cls < C, "mts_crf_marginals: cls must be in 0..C-1");
   MTS_CHECK_ARG(feats && trans && scores && workspace, "mts_crf_marginals: null pointer");
-  hipStream_t st = (hipStream_t)stream;
-  if (C == 4) hipLaunchKernelGGL(crf_marg4_kernel, dim3(ceil_div(B, 16)), dim3(64), 0, st, B, L, cls, feats, lengths, trans, scores, logz, workspace);
-  else hipLaunchKernelGGL(crf_marg_kernel, dim3(ceil_div(B, 64)), dim3(64), 0, st, B, L, C, cls, feats, lengths, trans, scores, logz, workspace);
-  MTS_LAUNCH_CHECK("mts_crf_marginals");
-  return MTS_OK;
+  return crf_marginals_launch((hipStream_t)stream, B, L, C, cls, feats, lengths, trans, scores, logz, workspace, nullptr, 0, "mts_crf_marginals");
+}
+
+extern "C" int mts_crf_marginals_packed(void* stream, int B, int L, int C, int cls, const float* feats, const int32_t* lengths, const float* trans,
+                                        float* scores, float* logz, float* workspace, const int32_t* row0, int n_rows) {
+  MTS_CHECK_ARG(B > 0 && L > 0 && C >= 3 && C <= CRF_MAXC && n_rows >= 0, "mts_crf_marginals_packed: bad shape (C must be in 3..8, n_rows >= 0)");
+  MTS_CHECK_ARG(cls >= 0 && cls < C, "mts_crf_marginals_packed: cls must be in 0..C-1");
+  MTS_CHECK_ARG(feats && trans && scores && workspace, "mts_crf_marginals_packed: null pointer");
+  MTS_CHECK_ARG(!row0 || lengths, "mts_crf_marginals_packed: packed rows need the lengths");
+  return crf_marginals_launch((hipStream_t)stream, B, L, C, cls, feats, lengths, trans, scores, logz, workspace, row0, n_rows, "mts_crf_marginals_packed");
 }

@@ -33,7 +33,8 @@ import torch.distributed as dist
 
 from . import ops
 from .fit import _forward, fit
-from .rnn_taggers import BiRnnCrf, SheikhBiLSTM
+from .rnn_taggers import SheikhBiLSTM
+from .taggers import decodes_by_viterbi
 from .threshold_search import FALLBACK_THRESHOLD, ThresholdSweep
 
 SIX_KEYS = ('Pk', 'WD', 'F1')
@@ -90,7 +91,7 @@ def evaluate(trainer_or_model, corpus, *, batch_size=8, threshold=None, end_boun
         raise ValueError('evaluate: the corpus has no documents')
     if not getattr(corpus, 'labelled', True):
         raise ValueError('evaluate: the corpus is unlabelled (ResidentCorpus.from_documents); predict is the pass that needs no labels')
-    viterbi = isinstance(model, BiRnnCrf) and model.decode == 'viterbi'
+    viterbi = decodes_by_viterbi(model)                # BiRnnCrf / TransformerCRF in their default decode
     m = 1 if min_segment is None else int(min_segment)
     if m < 1:
         raise ValueError(f'evaluate: min_segment={min_segment}; a segment holds at least one sentence')

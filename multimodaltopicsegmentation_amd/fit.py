@@ -26,7 +26,8 @@ clone of ``model.flat`` with the epoch's threshold; ``restore_best`` copies it b
 import torch
 import torch.distributed as dist
 
-from .rnn_taggers import BiRnnCrf, SheikhBiLSTM
+from .rnn_taggers import SheikhBiLSTM
+from .taggers import decodes_by_viterbi
 from .threshold_search import ThresholdSweep
 
 
@@ -69,8 +70,8 @@ def monitor_mode(search_threshold, metric):
 
 def _refusal(model, metric):
     """Why a threshold cannot be searched for this model and metric (TextSegmenter._sweep_refusal's reasons), or None."""
-    if isinstance(model, BiRnnCrf) and model.decode == 'viterbi':
-        return "search_threshold: architecture 'biLSTMCRF' decodes by Viterbi and has no decision threshold to search"
+    if decodes_by_viterbi(model):
+        return f"search_threshold: architecture '{model.crf_architecture}' decodes by Viterbi and has no decision threshold to search"
     if str(metric).lower() == 'b':
         return (f"search_threshold: metric '{metric}' (B-measure) needs the third-party package segeval and is not in the threshold-sweep "
                 "kernels; use 'Pk', 'WD', 'F1' or 'scaiano'")

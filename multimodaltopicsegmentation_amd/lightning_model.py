@@ -14,7 +14,8 @@ import torch.nn as nn
 from . import metrics
 from .rnn_taggers import BiLSTM, BiLSTMLateFusion, BiRnnCrf, SheikhBiLSTM, SwitchBiLSTM
 from .t5_taggers import RecurrentLongT5
-from .taggers import Transformer_segmenter
+from .crf_taggers import TransformerCRF
+from .taggers import Transformer_segmenter, decodes_by_viterbi
 from .threshold_search import ThresholdSweep
 
 try:  # pragma: no cover - not installed in the build image
@@ -44,7 +45,7 @@ except Exception:  # noqa: BLE001
             return obj
 
 # architectures of the reference that are outside the hot path
-_OUT_OF_SCOPE = ('SimpleBiLSTM', 'MLP', 'Transformer-CRF', 'BiLSTMRestrictedMHA')
+_OUT_OF_SCOPE = ('SimpleBiLSTM', 'MLP', 'BiLSTMRestrictedMHA')
 
 
 class TextSegmenter(_Base):
@@ -56,12 +57,13 @@ class TextSegmenter(_Base):
                  crf_decode='viterbi'):
         super().__init__()
         self.validation = not no_validation
-        # crf_decode (extension, default 'viterbi'): 'marginal' makes architecture='biLSTMCRF' score every sentence with the logit of its
-        # posterior marginal and decode by prob > th (BiRnnCrf(decode='marginal')), so threshold, search_threshold and all_scores apply to it
+        # crf_decode (extension, default 'viterbi'): 'marginal' makes architecture='biLSTMCRF' / 'Transformer-CRF' score every sentence with the
+        # logit of its posterior marginal and decode by prob > th (BiRnnCrf / TransformerCRF(decode='marginal')), so threshold, search_threshold
+        # and all_scores apply to it
         if crf_decode not in BiRnnCrf.DECODES:
             raise ValueError(f'crf_decode must be one of {BiRnnCrf.DECODES}, got {crf_decode!r}')
-        if crf_decode != 'viterbi' and architecture != 'biLSTMCRF':
-            raise ValueError(f"crf_decode='{crf_decode}' applies to architecture='biLSTMCRF' only, not to '{architecture}'")
+        if crf_decode != 'viterbi' and architecture not in ('biLSTMCRF', 'Transformer-CRF'):
+            raise ValueError(f"crf_decode='{crf_decode}' applies to architecture='biLSTMCRF' and 'Transformer-CRF' only, not to '{architecture}'")
         # fusion_merge (extension, default 'concat'): 'gate' makes architecture='BiLSTMLateFusion' merge its two encoders through a learned
         # sigmoid gate instead of concatenating them (BiLSTMLateFusion(merge='gate')); no other architecture has two encoders to merge
         if fusion_merge not in BiLSTMLateFusion.MERGES:
@@ -94,6 +96,12 @@ class TextSegmenter(_Base):
                                                positional_encoding=positional_encoding, nheads=nheads, threshold=threshold,
                                                alpha=alpha, gamma=gamma, window_size=attention_window, compute_dtype=compute_dtype,
                                                restricted=restricted)
+        elif architecture == 'Transformer-CRF':
+            # lightning_model.py:203-205; attention_window, restricted and crf_decode are extensions (upstream's class cannot be constructed)
+            self.cos = False
+            self.model = TransformerCRF(tagset_size, embedding_dim, hidden_dim, num_layers=num_layers, nheads=nheads, dropout_in=dropout_in,
+                                        dropout_out=dropout_out, batch_first=batch_first, positional_encoding=positional_encoding,
+                                        restricted=restricted, window_size=attention_window, decode=crf_decode, compute_dtype=compute_dtype)
         elif architecture == 'RecurrentLongT5':
             self.model = RecurrentLongT5(tagset_size, embedding_dim, hidden_dim, num_layers=num_layers, dropout_in=dropout_in,
                                          dropout_out=dropout_out, batch_first=batch_first, loss_fn=loss_fn, nheads=nheads, threshold=threshold,
@@ -207,8 +215,8 @@ class TextSegmenter(_Base):
 
     def _sweep_refusal(self):
         """Why the threshold sweep does not apply to this model, or None."""
-        if isinstance(self.model, BiRnnCrf) and self.model.decode == 'viterbi':
-            return "search_threshold: architecture 'biLSTMCRF' decodes by Viterbi and has no decision threshold to search"
+        if decodes_by_viterbi(self.model):
+            return f"search_threshold: architecture '{self.model.crf_architecture}' decodes by Viterbi and has no decision threshold to search"
         if self.metric.lower() in ('b', 'scaiano'):
             return f"search_threshold: metric '{self.metric}' (B-measure / WinPR) is not in the threshold-sweep kernel; use 'Pk', 'WD' or 'F1'"
         return None

@@ -902,6 +902,31 @@ def crf_marginals(feats, lengths, trans, scores, cls=1, logz=None):
     check(lib.mts_crf_marginals(stream_ptr(), B, Lq, C, int(cls), ptr(feats), ptr(lengths), ptr(trans), ptr(scores), ptr(logz), ptr(ws)))
 
 
+# ---- the CRF on packed rows (include/mts.h): feats fp32 [n_rows, C], document b in rows row0[b] .. row0[b] + len_b - 1; B and L (the
+# longest document the kernels walk) come with ``shape``; row0 = None is the padded layout ([B * L, C] rows)
+def crf_nll_packed(feats, tags, lengths, trans, loss_out, shape, row0=None, dfeats=None, dtrans=None):
+    (B, Lq), (n_rows, C) = shape, feats.shape
+    ws = _scratch(lib.mts_crf_workspace(B, Lq, C), feats.device, 'crf')
+    check(lib.mts_crf_nll_packed(stream_ptr(), B, Lq, C, ptr(feats), ptr(tags), tags.shape[1], ptr(lengths), ptr(trans), ptr(loss_out),
+                                 ptr(dfeats), ptr(dtrans), ptr(ws), ptr(row0), n_rows))
+
+
+def crf_viterbi_packed(feats, lengths, trans, best_score, paths, row0=None):
+    """paths int32 [B, L] (-1 past a document's length), best_score fp32 [B]"""
+    (B, Lq), (n_rows, C) = paths.shape, feats.shape
+    ws = _scratch(max(n_rows, 1) * C * 4, feats.device, 'crf_bp')
+    check(lib.mts_crf_viterbi_packed(stream_ptr(), B, Lq, C, ptr(feats), ptr(lengths), ptr(trans), ptr(best_score), ptr(paths), ptr(ws),
+                                     ptr(row0), n_rows))
+
+
+def crf_marginals_packed(feats, lengths, trans, scores, shape, row0=None, cls=1, logz=None):
+    """scores fp32 [n_rows]: the clamped logit of P(y_t = cls | x) of every packed row"""
+    (B, Lq), (n_rows, C) = shape, feats.shape
+    ws = _scratch(lib.mts_crf_workspace(B, Lq, C), feats.device, 'crf')
+    check(lib.mts_crf_marginals_packed(stream_ptr(), B, Lq, C, int(cls), ptr(feats), ptr(lengths), ptr(trans), ptr(scores), ptr(logz), ptr(ws),
+                                       ptr(row0), n_rows))
+
+
 def adam_step(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, grad_scale=1.0, bf16_copy=None):
     check(lib.mts_adam_step(stream_ptr(), param.numel(), ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), lr, beta1, beta2,
                             eps, step, grad_scale, ptr(bf16_copy)))

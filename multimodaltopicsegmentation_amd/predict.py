@@ -30,7 +30,8 @@ import torch.distributed as dist
 from . import ops
 from .evaluate import _saturated, _unwrap
 from .fit import _forward
-from .rnn_taggers import BiRnnCrf, SheikhBiLSTM
+from .rnn_taggers import SheikhBiLSTM
+from .taggers import decodes_by_viterbi
 from .threshold_search import FALLBACK_THRESHOLD
 
 POOL_MODES = ('mean', 'max', 'mean_std', 'max_std')
@@ -183,7 +184,7 @@ def predict(trainer_or_model, corpus, *, batch_size=8, threshold=None, min_segme
     m = int(min_segment)
     if m < 1:
         raise ValueError(f'predict: min_segment={min_segment}; a segment holds at least one sentence')
-    viterbi = isinstance(model, BiRnnCrf) and model.decode == 'viterbi'
+    viterbi = decodes_by_viterbi(model)                # BiRnnCrf / TransformerCRF in their default decode
     if viterbi and m > 1:
         raise ValueError("predict: min_segment > 1 needs probabilities; BiRnnCrf(decode='viterbi') has a path, not scores "
                          "(decode='marginal' gives them)")

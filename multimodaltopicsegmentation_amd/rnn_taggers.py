@@ -598,6 +598,8 @@ class BiRnnCrf(_RnnTaggerBase):
     logit of its posterior marginal P(y_t = 1 | x) (mts_crf_marginals) and decodes by ``sigmoid(score) > th`` like the other taggers, so the
     threshold sweeps apply.  It needs tagset_size == 2 (class 1 must be a real tag).  ``decode`` is not state: the parameters, the loss and
     the state_dict are those of the default model."""
+    crf_head = True
+    crf_architecture = 'biLSTMCRF'
     DECODES = ('viterbi', 'marginal')
     _GUARDED_ENTRY_POINTS = _TaggerBase._GUARDED_ENTRY_POINTS + ('marginal_scores',)
 

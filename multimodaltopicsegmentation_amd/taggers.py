@@ -7,6 +7,7 @@ error behaviour and ``state_dict`` keys as the reference:
     BiLSTM                  models/CRF.py:274-369  (+ RNN, NeuralArchitectures.py:23-145)
     BiLSTMLateFusion        models/CRF.py:371-479
     BiRnnCrf / CRF          models/CRF.py:243-272, :98-240   (the reference wrapper crashes; this one works)
+    TransformerCRF          models/CRF.py:481-506            (crf_taggers.py: this file's encoder under the CRF head)
 
 The arithmetic runs ONLY in libmts_hip.so (see include/mts.h); there is no PyTorch fallback.  Every model keeps
 its parameters in one flat fp32 buffer (flat.py) and has two front-ends over the same kernels:
@@ -144,6 +145,8 @@ class _TaggerBase(FlatModule):
             self._wcopy_version = ver
         return self._wcopy
 
+    crf_head = False                 # True: a CRF head (BiRnnCrf, TransformerCRF) -- ``decode`` is 'viterbi' (forward returns paths, no decision
+                                     # threshold) or 'marginal' (1-wide logits); fit / evaluate / predict / TextSegmenter ask decodes_by_viterbi()
     loss_grad_scale = 1.0            # multiplies d loss / d scores (trainer.NativeTrainer: token-weighted data parallelism)
     _grad_hook = None
     grad_hooks_cover_all = False     # subclasses that announce every parameter span through _grads_ready set this
@@ -419,21 +422,27 @@ class _NativeLoss(torch.autograd.Function):
         return (None, None, *grads)
 
 
+def decodes_by_viterbi(model):
+    """True for a CRF-headed tagger in its default decode: ``forward`` returns (path score, paths), there is no decision threshold to
+    search and no probability for a constrained decode (fit._refusal, evaluate, predict, TextSegmenter._sweep_refusal)."""
+    return bool(getattr(model, 'crf_head', False)) and getattr(model, 'decode', 'viterbi') == 'viterbi'
+
+
 # =====================================================================================================
 # Restricted-window transformer tagger
 # =====================================================================================================
-class Transformer_segmenter(_TaggerBase):
-    """models/CRF.py:508-610: encoder + linear head.  restricted=True: HF-Longformer-style local attention (pyramidal windows);
-    restricted=False: the BertModel of Classic_Transformer (models/RestrictedTransformerLayer.py:16-63) -- full attention over
-    each document's valid sentences, positions 0..L-1, attention dropout 0.1 in training (BertConfig's default; dropout_out and
-    window_size are not used there)."""
-    grad_hooks_cover_all = True
+class _TransformerEncoderTagger(_TaggerBase):
+    """The encoder of Transformer_segmenter with a linear head of ``n_out`` outputs fused into its last LayerNorm, shared by the taggers
+    that differ only in what reads the head's outputs (Transformer_segmenter: a pointwise loss; crf_taggers.TransformerCRF: a CRF).
+    A subclass names the head's two tensors (_HEAD_W [n_out, D], _HEAD_B [n_out]) and appends its own groups in ``_head_groups``."""
+    _HEAD_W, _HEAD_B = 'classification.weight', 'classification.bias'
 
-    def __init__(self, tagset_size, embedding_dim, hidden_dim, num_layers=6, nheads=8, dropout_in=0.0, dropout_out=0.0,
-                 batch_first=True, loss_fn='CrossEntropy', positional_encoding=True, threshold=None, restricted=True,
-                 window_size=127, alpha=0.9, gamma=2, compute_dtype=None, max_position_embedding=4096, seed=None):
-        super().__init__()
-        self._init_common(loss_fn, threshold, alpha, gamma, compute_dtype)
+    def _head_groups(self, gen, add):
+        """-> the layout groups behind the encoder's (the head first: its two tensors adjacent), filled through add(group, name, shape, value)"""
+        raise NotImplementedError
+
+    def _init_encoder(self, tagset_size, embedding_dim, hidden_dim, num_layers, nheads, dropout_in, dropout_out, restricted, window_size,
+                      max_position_embedding, seed, n_out):
         self.restricted = bool(restricted)
         # dropout_in -> HF hidden_dropout_prob (embeddings, attention-output and FFN-output dense layers; training mode only),
         # dropout_out -> attention_probs_dropout_prob (RestrictedTransformerLayer.py:88-89)
@@ -459,7 +468,7 @@ class Transformer_segmenter(_TaggerBase):
             self.radii = [None] * num_layers              # None: full attention (window_size is not used)
         if embedding_dim % nheads != 0:
             raise ValueError(f'The hidden size ({embedding_dim}) is not a multiple of the number of attention heads ({nheads})')
-        self.n_out = tagset_size if loss_fn == 'CrossEntropy' else 1
+        self.n_out = n_out
         self.ln_eps = 1e-12                                # HF default; the wrapper's layer_norm_eps is ignored
         self.max_pos = max_position_embedding
         D, F = embedding_dim, hidden_dim
@@ -522,11 +531,7 @@ class Transformer_segmenter(_TaggerBase):
                 else:
                     add(g, lp + name, shape, val)
                 groups.append(g)
-        cw, cb = _linear_init(self.n_out, D, gen)
-        g = []
-        add(g, 'classification.weight', (self.n_out, D), cw)
-        add(g, 'classification.bias', (self.n_out,), cb)
-        groups.append(g)
+        groups += self._head_groups(gen, add)
         self._init_flat(FlatLayout(groups, pads), init)
         self._register_load_state_dict_pre_hook(self._drop_dead_keys)
 
@@ -587,7 +592,7 @@ class Transformer_segmenter(_TaggerBase):
         scores = ws.get('scores', N, self.n_out, torch.float32, dev)
         for li, radius in enumerate(self.radii):
             last = li == len(self.radii) - 1
-            head = (self._w(pf, 'classification.weight'), self._w(pf, 'classification.bias'), scores) if (last and not tail) else None
+            head = (self._w(pf, self._HEAD_W), self._w(pf, self._HEAD_B), scores) if (last and not tail) else None
             S = self._band_layer_fwd(self._layer_names(li), str(li), h, lengths_i32, B, Lq, N, radius, row0, pdrop,
                                      self._attn_drop if self.training else 0.0, head,
                                      # (a head wider than two outputs takes its parameter gradients from the stored output: _backward_native)
@@ -634,12 +639,12 @@ class Transformer_segmenter(_TaggerBase):
             # training forward does not even write); a head wider than two outputs keeps its own kernel
             fuse_hg = last and self.n_out <= 2 and not tail_done
             if last and not fuse_hg and not tail_done:
-                ops.head_bwd_params(st['layers'][li]['hout'], dscores, G('classification.weight'), G('classification.bias'))
+                ops.head_bwd_params(st['layers'][li]['hout'], dscores, G(self._HEAD_W), G(self._HEAD_B))
             tail_end = lay.entries[f'model.model.encoder.layer.{li + 1}.attention.self.query.weight'][0] if li + 1 < nl else g.numel()
             dh = self._band_layer_bwd(self._layer_names(li), st['layers'][li], dh, st['lengths'], B, Lq, N, st['pdrop'],
                                       st['pack']['row0'] if st['pack'] else None, wgrad, tail_end,
-                                      head=(dscores, self._w(pf, 'classification.weight')) if (last and not tail_done) else None, slot=li & 1,
-                                      head_grads=(G('classification.weight'), G('classification.bias')) if fuse_hg else None,
+                                      head=(dscores, self._w(pf, self._HEAD_W)) if (last and not tail_done) else None, slot=li & 1,
+                                      head_grads=(G(self._HEAD_W), G(self._HEAD_B)) if fuse_hg else None,
                                       tail_done=tail_done and last, wgrad_direct=side is None)
         e = 'model.model.embeddings.'
         if st['pdrop']:
@@ -711,6 +716,35 @@ class Transformer_segmenter(_TaggerBase):
             self._pack_key = key
         return self._pack_val
 
+    def encode(self, xs, lengths):
+        """Encoder output [B, L, D] (``Longformer_Local_Attention.forward``, RestrictedTransformerLayer.py:118-133)."""
+        x1, _, B, Lq, _ = self._split_input(xs)
+        st = self._forward_native(xs, self._prep_lengths(lengths, B, Lq, x1.device))
+        return st['hidden'].view(B, Lq, -1).to(torch.float32)
+
+
+class Transformer_segmenter(_TransformerEncoderTagger):
+    """models/CRF.py:508-610: encoder + linear head.  restricted=True: HF-Longformer-style local attention (pyramidal windows);
+    restricted=False: the BertModel of Classic_Transformer (models/RestrictedTransformerLayer.py:16-63) -- full attention over
+    each document's valid sentences, positions 0..L-1, attention dropout 0.1 in training (BertConfig's default; dropout_out and
+    window_size are not used there)."""
+    grad_hooks_cover_all = True
+
+    def __init__(self, tagset_size, embedding_dim, hidden_dim, num_layers=6, nheads=8, dropout_in=0.0, dropout_out=0.0,
+                 batch_first=True, loss_fn='CrossEntropy', positional_encoding=True, threshold=None, restricted=True,
+                 window_size=127, alpha=0.9, gamma=2, compute_dtype=None, max_position_embedding=4096, seed=None):
+        super().__init__()
+        self._init_common(loss_fn, threshold, alpha, gamma, compute_dtype)
+        self._init_encoder(tagset_size, embedding_dim, hidden_dim, num_layers, nheads, dropout_in, dropout_out, restricted, window_size,
+                           max_position_embedding, seed, tagset_size if loss_fn == 'CrossEntropy' else 1)
+
+    def _head_groups(self, gen, add):
+        cw, cb = _linear_init(self.n_out, self.embedding_dim, gen)
+        g = []
+        add(g, 'classification.weight', (self.n_out, self.embedding_dim), cw)
+        add(g, 'classification.bias', (self.n_out,), cb)
+        return [g]
+
     # ---- public API ------------------------------------------------------------------------------------
     def loss_and_grad(self, xs, lengths, tags, want_grad=True):
         """Native forward(+backward): returns (loss 0-d fp32 tensor, scores [B,L,n_out] -- or [n_valid, n_out] when the batch
@@ -753,12 +787,6 @@ class Transformer_segmenter(_TaggerBase):
         if torch.is_grad_enabled() and any(p.requires_grad for p in self._flat_params.values()):
             return self._autograd_loss(lambda: self.loss_and_grad(xs, lengths, tags, True)[0])
         return self.loss_and_grad(xs, lengths, tags, False)[0].clone()
-
-    def encode(self, xs, lengths):
-        """Encoder output [B, L, D] (``Longformer_Local_Attention.forward``, RestrictedTransformerLayer.py:118-133)."""
-        x1, _, B, Lq, _ = self._split_input(xs)
-        st = self._forward_native(xs, self._prep_lengths(lengths, B, Lq, x1.device))
-        return st['hidden'].view(B, Lq, -1).to(torch.float32)
 
     # Inference at one document per call is launch-bound (a dozen kernels of a few microseconds each): with inference_graphs = True
     # the forward + decode of a given (B, L) shape is captured once as a hipGraph (torch.cuda.CUDAGraph: the kernels are enqueued
