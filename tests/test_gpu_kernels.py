@@ -329,6 +329,7 @@ def test_colsum_cast(ops, dtype):
 @pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize('D', [64, 96, 1792, 2304])
 def test_layernorm_fwd_bwd(ops, dtype, D):
+    """(every width / row count / head form of these two entry points: tests/test_gpu_norm_regimes.py)"""
     rows, eps = 301, 1e-12
     x = (_rnd(rows, D, seed=11) * 1.7 + 0.3).to(dtype)
     gam, bet = 1 + 0.1 * _rnd(D, seed=12), 0.1 * _rnd(D, seed=13)
@@ -363,6 +364,7 @@ def test_layernorm_fwd_bwd(ops, dtype, D):
 
 @pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
 def test_embed_layernorm_and_bwd(ops, dtype):
+    """(bf16 / two-part input, packed batches and the document loop of embed_bwd: tests/test_gpu_norm_regimes.py)"""
     B, Lq, D, eps = 3, 37, 96, 1e-12
     x = _rnd(B, Lq, D, seed=18)
     pos = _rnd(64, D, seed=19, scale=0.5)
@@ -386,6 +388,7 @@ def test_embed_layernorm_and_bwd(ops, dtype):
 
 @pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
 def test_gelu_bwd_and_head(ops, dtype):
+    """(the head at every n_out, in column windows, accumulating, past one grid pass and two chunks wide: tests/test_gpu_norm_regimes.py)"""
     u = _rnd(77, 64, seed=24, scale=2).to(dtype)
     dy = _rnd(77, 64, seed=25).to(dtype)
     dyd = dy.to(DEV).clone()
