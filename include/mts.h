@@ -717,7 +717,12 @@ int mts_switch_head_bwd_data(void* stream, int dtype, int B, int L, int D, int n
  *   added to the gate pre-activations in fp32 inside the recurrence.
  * out: [B*L, ndir*H] act dtype.  gates (saved for backward): act dtype, B*L*ndir*4H elements, post-activation
  *   i,f,g,o; cells: fp32, B*L*ndir*H elements.  Both are OPAQUE saved state handed unchanged to mts_lstm_bwd under the same options
- *   (the generic kernels keep them as [B*L, ndir*4H] / [B*L, ndir*H]; the bf16 CU-quad recurrences keep step-major blocks).
+ *   (the generic and the persistent-MFMA kernels keep them as [B*L, ndir*4H] / [B*L, ndir*H]; the bf16 CU-quad recurrences keep
+ *   step-major blocks).
+ * lengths int32 [B], NULL = every document has L sentences (clamped to 0..L): a document of length 0 gets rows of exact zeros in out
+ *   and dxproj and contributes nothing to dw_hh; ndir is 1 (forward direction only) or 2 in every form.
+ * bf16 with H % 8 != 0, fp32 with H % 4 != 0: the forward and mts_lstm_bwd_recurrence run, mts_lstm_bwd / mts_lstm_bwd_whh return
+ *   MTS_ERR_UNSUPPORTED before any launch (the dW_hh GEMM needs such rows; the taggers pad the hidden size to a multiple of 8).
  * ------------------------------------------------------------------------------------------- */
 /* workspace (both calls): mts_lstm_workspace(dtype, B, L, H, ndir) bytes */
 size_t mts_lstm_workspace(int dtype, int B, int L, int H, int ndir);

@@ -32,7 +32,7 @@ __global__ void lstm_fwd_kernel(int B, int L, int H, int ndir, const T* __restri
 #pragma unroll
   for (int q = 0; q < LSTM_DG; ++q) {
     const int b = b0 + q;
-    len[q] = (b < B) ? (lengths ? min(lengths[b], L) : L) : 0;
+    len[q] = (b < B) ? (lengths ? max(min(lengths[b], L), 0) : L) : 0;
     maxlen = max(maxlen, len[q]);
   }
   float c[LSTM_DG];
@@ -120,7 +120,7 @@ __global__ void lstm_bwd_kernel(int B, int L, int H, int ndir, const float* __re
 #pragma unroll
   for (int q = 0; q < LSTM_DG; ++q) {
     const int b = b0 + q;
-    len[q] = (b < B) ? (lengths ? min(lengths[b], L) : L) : 0;
+    len[q] = (b < B) ? (lengths ? max(min(lengths[b], L), 0) : L) : 0;
     maxlen = max(maxlen, len[q]);
   }
   float dh[LSTM_DG], dc[LSTM_DG];
@@ -213,7 +213,7 @@ int mts_lstm_mfma_fwd(hipStream_t st, int B, int L, int H, int ndir, const void*
                       const int32_t* lengths, void* out, void* gates, float* cells, void* ws);
 int mts_lstm_mfma_bwd(hipStream_t st, int B, int L, int H, int ndir, const float* w_hh, const int32_t* lengths, const void* out, const void* gates,
                       const float* cells, const void* dout, void* dxproj, void* hprev, void* ws);
-// CU-pair form (lstm_pair.hip): weights fully register-resident, forward only so far
+// CU-pair / CU-quad forms (lstm_pair.hip): weights fully register-resident, forward and backward
 bool mts_lstm_pair_supported(int dtype, int H);
 size_t mts_lstm_pair_workspace(int B, int H, int ndir);
 int mts_lstm_pair_fwd(hipStream_t st, int B, int L, int H, int ndir, const void* xproj, const float* w_hh, const float* b_hh,
@@ -319,6 +319,10 @@ static int lstm_bwd_impl(int part, void* stream, int dtype, int B, int L, int H,
   MTS_CHECK_ARG(!(part & 2) || dw_hh, "%s: null pointer", who);
   MTS_CHECK_ARG(dtype == MTS_F32 || dtype == MTS_BF16, "%s: bad dtype %d", who, dtype);
   MTS_UNSUPPORTED(H <= 1024, "%s: hidden size %d > 1024", who, H);
+  // the dW_hh GEMMs need rows of 8 bf16 / 4 fp32 elements (mts_gemm: operand and ldc alignment): refuse before the recurrence is launched, not
+  // after it.  The taggers never get here with such a size: they pad the hidden size to a multiple of 8 in storage.
+  MTS_UNSUPPORTED(!(part & 2) || dtype == MTS_F32 || H % 8 == 0, "%s(bf16): hidden size %d must be a multiple of 8", who, H);
+  MTS_UNSUPPORTED(!(part & 2) || dtype != MTS_F32 || H % 4 == 0, "%s(f32): hidden size %d must be a multiple of 4", who, H);
   if (int rc = lstm_report_async(who)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const size_t hoff = lstm_scratch_bytes(B, H, ndir);
@@ -360,8 +364,6 @@ static int lstm_bwd_impl(int part, void* stream, int dtype, int B, int L, int H,
   }
   // dW_hh[d] = dA_d^T [4H, B*L] . Hprev_d [B*L, H]
   const size_t esz = dtype == MTS_F32 ? 4 : 2;
-  const bool mfma_ok = (dtype == MTS_F32) || ((4 * H) % 8 == 0 && H % 8 == 0 && (ndir * 4 * H) % 8 == 0 && (ndir * H) % 8 == 0);
-  MTS_UNSUPPORTED(mfma_ok, "%s(bf16): hidden size %d must be a multiple of 8", who, H);
   for (int d = 0; d < ndir; ++d) {
     int rc = mts_gemm(stream, dtype, MTS_F32, MTS_TN, 4 * H, H, B * L, (const char*)dxproj + (size_t)d * 4 * H * esz, ndir * 4 * H,
                       hprev + (size_t)d * H * esz, ndir * H, dw_hh + (size_t)d * 4 * H * H, H, nullptr, nullptr, 0, nullptr, 0, 0u, 1.f, 0,

@@ -64,7 +64,7 @@ __global__ __launch_bounds__(KS * 64, 2) void lstm_fwd_mfma_kernel(int B, int L,
   const bf16_t* W = whh + (size_t)d * 4 * H * H;
 
   const int bdoc = b0 + doc;
-  const int len = (bdoc < B) ? (lengths ? min(lengths[bdoc], L) : L) : 0;
+  const int len = (bdoc < B) ? (lengths ? max(min(lengths[bdoc], L), 0) : L) : 0;
   int maxlen = len;
 #pragma unroll
   for (int off = 1; off < 16; off <<= 1) maxlen = max(maxlen, __shfl_xor(maxlen, off, 64));
@@ -247,7 +247,7 @@ __global__ __launch_bounds__(KS * 64, 2) void lstm_bwd_mfma_kernel(int B, int L,
   const bf16_t* WT = whhT + (size_t)d * 4 * H * H;
 
   const int bdoc = b0 + doc;
-  const int len = (bdoc < B) ? (lengths ? min(lengths[bdoc], L) : L) : 0;
+  const int len = (bdoc < B) ? (lengths ? max(min(lengths[bdoc], L), 0) : L) : 0;
   int maxlen = len;
 #pragma unroll
   for (int off = 1; off < 16; off <<= 1) maxlen = max(maxlen, __shfl_xor(maxlen, off, 64));

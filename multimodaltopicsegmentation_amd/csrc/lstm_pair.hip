@@ -125,7 +125,7 @@ __global__ __launch_bounds__(KS * 64, 2) void lstm_fwd_pair_kernel(int B, int L,
 #pragma unroll
   for (int g = 0; g < LP_GROUPS; ++g) {
     bdoc[g] = (gx * LP_GROUPS + g) * LP_DOCS + doc;
-    len[g] = (bdoc[g] < B) ? (lengths ? min(lengths[bdoc[g]], L) : L) : 0;
+    len[g] = (bdoc[g] < B) ? (lengths ? max(min(lengths[bdoc[g]], L), 0) : L) : 0;
     maxlen = max(maxlen, len[g]);
   }
 #pragma unroll
@@ -484,7 +484,7 @@ __global__ __launch_bounds__(KS * 64, 2) void lstm_bwd_pair_kernel(int B, int L,
   }
 
   const int bdoc = gx * LP_DOCS + doc;
-  const int len = (bdoc < B) ? (lengths ? min(lengths[bdoc], L) : L) : 0;
+  const int len = (bdoc < B) ? (lengths ? max(min(lengths[bdoc], L), 0) : L) : 0;
   int maxlen = len;
 #pragma unroll
   for (int off = 1; off < 16; off <<= 1) maxlen = max(maxlen, __shfl_xor(maxlen, off, 64));
@@ -671,7 +671,7 @@ __global__ __launch_bounds__(256, 1) void lstm_fwd_quad_kernel(int B, int L, int
   for (int i = tid; i < 4 * HQ; i += NT) blds[i] = bhh ? bhh[(size_t)d * 4 * H + (i / HQ) * H + p * HQ + (i % HQ)] : 0.f;
 
   const int bdoc = gx * LP_DOCS + doc;
-  const int len = (bdoc < B) ? (lengths ? min(lengths[bdoc], L) : L) : 0;
+  const int len = (bdoc < B) ? (lengths ? max(min(lengths[bdoc], L), 0) : L) : 0;
   int maxlen = len;
 #pragma unroll
   for (int off = 1; off < 16; off <<= 1) maxlen = max(maxlen, __shfl_xor(maxlen, off, 64));
@@ -913,7 +913,7 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd_quad_kernel(int B, int L, int
   }
 
   const int bdoc = gx * LP_DOCS + doc;
-  const int len = (bdoc < B) ? (lengths ? min(lengths[bdoc], L) : L) : 0;
+  const int len = (bdoc < B) ? (lengths ? max(min(lengths[bdoc], L), 0) : L) : 0;
   int maxlen = len;
 #pragma unroll
   for (int off = 1; off < 16; off <<= 1) maxlen = max(maxlen, __shfl_xor(maxlen, off, 64));
@@ -1073,7 +1073,7 @@ __global__ void lstm_hprev_kernel(int B, int L, int H, int ndir, const int32_t* 
   const size_t row = idx / per_row;
   const int c = (int)(idx % per_row) * 4, d = c / H;
   const int b = (int)(row / L), t = (int)(row % L);
-  const int len = lengths ? min(lengths[b], L) : L;
+  const int len = lengths ? max(min(lengths[b], L), 0) : L;
   float v[4] = {0.f, 0.f, 0.f, 0.f};
   const int tp = (d == 0) ? t - 1 : t + 1;
   if (t < len && tp >= 0 && tp < len) load4<T>(out + ((size_t)b * L + tp) * ndir * H + c, v);
@@ -1222,7 +1222,7 @@ __global__ __launch_bounds__(256, 1) void lstm_fwd_quad_f32_kernel(int B, int L,
     for (int r = 0; r < 4; ++r) bia[gt][r] = bhh ? bhh[(size_t)d * 4 * H + gt * H + u + r] : 0.f;
 
   const int bdoc = gx * LP_DOCS + doc;
-  const int len = (bdoc < B) ? (lengths ? min(lengths[bdoc], L) : L) : 0;
+  const int len = (bdoc < B) ? (lengths ? max(min(lengths[bdoc], L), 0) : L) : 0;
   int maxlen = len;
 #pragma unroll
   for (int off = 1; off < 16; off <<= 1) maxlen = max(maxlen, __shfl_xor(maxlen, off, 64));
@@ -1388,7 +1388,7 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd_quad_f32_kernel(int B, int L,
       for (int ks = 0; ks < 64; ++ks) wreg[tt][ks] = base[(size_t)(tt * 64 + ks) * 64 + lane];
   }
   const int bdoc = gx * LP_DOCS + doc;
-  const int len = (bdoc < B) ? (lengths ? min(lengths[bdoc], L) : L) : 0;
+  const int len = (bdoc < B) ? (lengths ? max(min(lengths[bdoc], L), 0) : L) : 0;
   int maxlen = len;
 #pragma unroll
   for (int off = 1; off < 16; off <<= 1) maxlen = max(maxlen, __shfl_xor(maxlen, off, 64));

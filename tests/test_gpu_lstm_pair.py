@@ -184,7 +184,7 @@ def test_two_concurrent_pair_grids_on_two_streams():
 
 
 @pytest.mark.parametrize('dt', [torch.bfloat16, torch.float32], ids=['bf16', 'fp32'])
-@pytest.mark.parametrize('H', [256, 32, 64], ids=['quad', 'generic', 'mfma_or_generic'])
+@pytest.mark.parametrize('H', [256, 32, 64], ids=['quad', 'generic', 'generic_h64'])
 def test_backward_in_two_calls_equals_the_single_call(H, dt):
     """mts_lstm_bwd_recurrence + mts_lstm_bwd_whh (the second on ANOTHER stream, behind an event, as the recurrent taggers issue them) against
     mts_lstm_bwd: dxproj and dW_hh bit for bit, on every recurrence path (CU-quad at H = 256; the kernels that build h_{t-1} themselves below)."""
