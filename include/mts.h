@@ -374,7 +374,10 @@ int mts_embed_bwd(void* stream, int dtype, int B, int L, int D, const void* dpre
 /* Inverted dropout: y = keep ? x / (1-p) : 0 (+ residual, if given), keep decided by a counter-based hash of (seed, element index)
  * (F.dropout in RNN.forward, NeuralArchitectures.py:94,119 -- active even in eval mode there; nn.Dropout of the HF layers,
  * modeling_longformer.py:424,1070,1129).  mask (optional, uint8 [n]) records keep = 1; x == y is allowed; n % 4 == 0.
- * mts_dropout_bwd: dx = mask ? dy / (1-p) : 0 (dx == dy allowed). */
+ * mts_dropout_bwd: dx = mask ? dy / (1-p) : 0 (dx == dy allowed).
+ * The kernels move 4 elements per access: x, residual, y, dy and dx must be aligned to 4 elements (16 bytes of fp32, 8 of bf16) and
+ * mask to 4 bytes.  A pointer off its boundary, n % 4 != 0, p outside [0, 1), a bad dtype or a null operand (the backward needs its
+ * mask) is MTS_ERR_INVALID before any launch; there is no scalar fallback. */
 int mts_dropout_fwd(void* stream, int dtype, size_t n, const void* x, const void* residual, void* y, uint8_t* mask,
                     float p, uint64_t seed);
 int mts_dropout_bwd(void* stream, int dtype, size_t n, const void* dy, void* dx, const uint8_t* mask, float p);
@@ -801,6 +804,9 @@ int mts_crf_marginals_packed(void* stream, int B, int L, int C, int cls, const f
  * Replaces torch.optim.Adam(eps=1e-7) / SGD(momentum .9, wd 1e-4) of models/lightning_model.py:759-765.
  * grad_scale multiplies the gradient first (1/world_size after an RCCL sum all-reduce).
  * If bf16_copy != NULL the updated parameters are also written as bf16 (next step's GEMM weights).
+ * mts_adam_step uses 16-byte accesses: param, grad and both moments must be 16-byte aligned and bf16_copy 8-byte aligned (a slice
+ * of the flat buffer has to begin on a multiple of 4 elements); any n.  mts_sgd_step works element by element: fp32 operands
+ * 4-byte, bf16_copy 2-byte aligned.  A pointer off its boundary is MTS_ERR_INVALID before any launch; there is no scalar fallback.
  * ------------------------------------------------------------------------------------------- */
 int mts_adam_step(void* stream, size_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
                   float lr, float beta1, float beta2, float eps, int step, float grad_scale, void* bf16_copy);

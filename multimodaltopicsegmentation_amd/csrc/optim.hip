@@ -169,9 +169,25 @@ __global__ __launch_bounds__(256) void sgd_clip_kernel(size_t n, float* __restri
   sgd_loop<CLIP>(n, p, g, buf, lr, mom, wd, first, gscale, copy, c);
 }
 
+// the vector accesses of adam_loop: 16 bytes on the fp32 operands, 8 on the bf16 copy (which may be NULL)
+static int check_adam_alignment(const char* name, const float* param, const float* grad, const float* exp_avg, const float* exp_avg_sq,
+                                const void* bf16_copy) {
+  MTS_CHECK_ARG(aligned_to(param, 16) && aligned_to(grad, 16) && aligned_to(exp_avg, 16) && aligned_to(exp_avg_sq, 16) && aligned_to(bf16_copy, 8),
+                "%s: param, grad and moments must be 16-byte aligned, bf16_copy 8-byte aligned", name);
+  return MTS_OK;
+}
+
+// sgd_loop works element by element: every operand on its element size
+static int check_sgd_alignment(const char* name, const float* param, const float* grad, const float* momentum_buf, const void* bf16_copy) {
+  MTS_CHECK_ARG(aligned_to(param, 4) && aligned_to(grad, 4) && aligned_to(momentum_buf, 4) && aligned_to(bf16_copy, 2),
+                "%s: param, grad and momentum_buf must be 4-byte aligned, bf16_copy 2-byte aligned", name);
+  return MTS_OK;
+}
+
 extern "C" int mts_adam_step(void* stream, size_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
                              float beta2, float eps, int step, float grad_scale, void* bf16_copy) {
   MTS_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && step >= 1, "mts_adam_step: bad arguments");
+  if (int rc = check_adam_alignment("mts_adam_step", param, grad, exp_avg, exp_avg_sq, bf16_copy)) return rc;
   if (n == 0) return MTS_OK;
   const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
   const int blocks = (int)std::min<size_t>(2048, (n / 4 + 255) / 256 + 1);
@@ -184,6 +200,7 @@ extern "C" int mts_adam_step(void* stream, size_t n, float* param, const float* 
 extern "C" int mts_sgd_step(void* stream, size_t n, float* param, const float* grad, float* momentum_buf, float lr, float momentum,
                             float weight_decay, int first_step, float grad_scale, void* bf16_copy) {
   MTS_CHECK_ARG(param && grad && momentum_buf, "mts_sgd_step: bad arguments");
+  if (int rc = check_sgd_alignment("mts_sgd_step", param, grad, momentum_buf, bf16_copy)) return rc;
   if (n == 0) return MTS_OK;
   const int blocks = (int)std::min<size_t>(2048, (n + 255) / 256);
   hipLaunchKernelGGL(sgd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, n, param, grad, momentum_buf, lr, momentum, weight_decay,
@@ -191,8 +208,6 @@ extern "C" int mts_sgd_step(void* stream, size_t n, float* param, const float* g
   MTS_LAUNCH_CHECK("mts_sgd_step");
   return MTS_OK;
 }
-
-static inline bool aligned_to(const void* p, size_t bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; }
 
 // total_norm != NULL selects the norm mode, total_norm == NULL with clip_value > 0 the value mode
 static int check_clip_args(const char* name, const float* total_norm, float max_norm, float clip_value) {
@@ -208,8 +223,7 @@ extern "C" int mts_adam_step_clipped(void* stream, size_t n, float* param, const
                                      float max_norm, float clip_value, float* clip_coef_out) {
   MTS_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && step >= 1, "mts_adam_step_clipped: bad arguments");
   if (int rc = check_clip_args("mts_adam_step_clipped", total_norm, max_norm, clip_value)) return rc;
-  MTS_CHECK_ARG(aligned_to(param, 16) && aligned_to(grad, 16) && aligned_to(exp_avg, 16) && aligned_to(exp_avg_sq, 16) && aligned_to(bf16_copy, 8),
-                "mts_adam_step_clipped: param, grad and moments must be 16-byte aligned, bf16_copy 8-byte aligned");
+  if (int rc = check_adam_alignment("mts_adam_step_clipped", param, grad, exp_avg, exp_avg_sq, bf16_copy)) return rc;
   MTS_CHECK_ARG(aligned_to(total_norm, 4) && aligned_to(clip_coef_out, 4), "mts_adam_step_clipped: misaligned scalar");
   if (n == 0) return MTS_OK;
   const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
@@ -226,9 +240,8 @@ extern "C" int mts_sgd_step_clipped(void* stream, size_t n, float* param, const 
                                     float max_norm, float clip_value, float* clip_coef_out) {
   MTS_CHECK_ARG(param && grad && momentum_buf, "mts_sgd_step_clipped: bad arguments");
   if (int rc = check_clip_args("mts_sgd_step_clipped", total_norm, max_norm, clip_value)) return rc;
-  MTS_CHECK_ARG(aligned_to(param, 4) && aligned_to(grad, 4) && aligned_to(momentum_buf, 4) && aligned_to(bf16_copy, 2) &&
-                    aligned_to(total_norm, 4) && aligned_to(clip_coef_out, 4),
-                "mts_sgd_step_clipped: misaligned operand");
+  if (int rc = check_sgd_alignment("mts_sgd_step_clipped", param, grad, momentum_buf, bf16_copy)) return rc;
+  MTS_CHECK_ARG(aligned_to(total_norm, 4) && aligned_to(clip_coef_out, 4), "mts_sgd_step_clipped: misaligned scalar");
   if (n == 0) return MTS_OK;
   const int blocks = (int)std::min<size_t>(2048, (n + 255) / 256);
   auto kernel = total_norm ? sgd_clip_kernel<CLIP_NORM> : sgd_clip_kernel<CLIP_VALUE>;

@@ -5,19 +5,15 @@ import numpy as np
 import pytest
 import torch
 
+from tests.stream_oracle import keep
+
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
 
 
 def _host_keep(n, p, seed):
-    idx = np.arange(1, n + 1, dtype=np.uint64)
-    with np.errstate(over='ignore'):
-        z = np.uint64(seed) + np.uint64(0x9E3779B97F4A7C15) * idx
-        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-        z = z ^ (z >> np.uint64(31))
-    thr = min(4294967295.0, p * 4294967296.0)
-    return (z >> np.uint64(32)).astype(np.float64) >= np.floor(thr)
+    """the kernel forms its keep threshold from the float32 p it receives (52 of 2^32 above the double's for p = 0.3): stream_oracle.keep does too"""
+    return keep(n, p, seed)
 
 
 @pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
