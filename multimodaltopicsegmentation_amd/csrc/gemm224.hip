@@ -17,7 +17,7 @@
 #include <algorithm>
 #include <type_traits>
 #include <math.h>
-#include "gemm_common.h"
+#include "gemm224_common.h"
 
 #if defined(MTS_GEMM_STAMPS) && !defined(G224_PHASES)
 #define STAMP(slot) do { if (a.stamps && tid == 0) { a.stamps[((size_t)blockIdx.x * 8 + round) * 8 + (slot)] = __builtin_amdgcn_s_memtime(); \
@@ -33,8 +33,6 @@
 #define A_BYTES (2 * HT_BYTES)
 #define B_BASE (3 * A_BYTES)
 #define LDS_TOTAL (3 * A_BYTES + 4 * HT_BYTES)
-#define BN224 224
-#define HN224 112
 
 #ifdef G224_PHASES                      // per-wave cycle sums per phase of the K loop (tools/micro/gemm224_phases.py); needs MTS_GEMM_STAMPS
 #define PST(i) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); pacc[i] += t_ - pprev; pprev = t_; } while (0)
@@ -152,76 +150,37 @@ __device__ __forceinline__ void store_tile_224(const GemmArgs& a, f32x4 (&acc)[4
 // without a single load in between, and nobody waits for the stores until two K-tiles into the next tile (EPI_STORES below).
 
 __device__ __forceinline__ bool epi224_fast_ok(const GemmArgs& a, int bm0) {
-  const unsigned simple = MTS_EPI_BIAS | MTS_EPI_COLSCALE | MTS_EPI_RESIDUAL;
-  return !a.slab && (a.epi & ~simple) == 0 && bm0 + 256 <= a.M && (a.ldc % 8 == 0) && (((uintptr_t)a.C & 15) == 0) &&
-         (!(a.epi & MTS_EPI_COLSCALE) || a.ncols_scaled % 4 == 0) &&
-         (!(a.epi & MTS_EPI_RESIDUAL) || (a.ldr % 4 == 0 && ((uintptr_t)a.residual & 7) == 0)) &&
-         (!(a.epi & MTS_EPI_BIAS) || ((uintptr_t)a.bias & 15) == 0);
+  return g224_simple_epi_ok(a, 8) && bm0 + 256 <= a.M && g224_c_bf16_ok(a);
 }
 
-// The fast epilogue is BRANCH-FREE so that every vector-memory wait in it can be counted: without a bias / residual the loads
-// still execute, from a few cache lines at the start of A (always mapped, >= 4 KiB), and their values are discarded by a select.
-struct Epi224 {
-  const float* bias_p; const bf16_t* res_p; size_t res_ld; bool has_bias, has_res; float colscale; int ncols_scaled;
-  __device__ __forceinline__ void init(const GemmArgs& a, int m0, int n0, bool first_slice, int lane) {
-    const int r16 = lane & 15, g = lane >> 4;
-    has_bias = (a.epi & MTS_EPI_BIAS) && first_slice;
-    has_res = (a.epi & MTS_EPI_RESIDUAL) && first_slice;
-    bias_p = has_bias ? a.bias + n0 + 4 * g : reinterpret_cast<const float*>(a.A) + 4 * g;
-    res_ld = has_res ? (size_t)a.ldr : 0;
-    res_p = has_res ? reinterpret_cast<const bf16_t*>(a.residual) + (size_t)(m0 + r16) * a.ldr + n0 + 4 * g
-                    : reinterpret_cast<const bf16_t*>(a.A) + 4 * g;
-    colscale = (a.epi & MTS_EPI_COLSCALE) ? a.colscale : 1.0f;
-    ncols_scaled = (a.epi & MTS_EPI_COLSCALE) ? a.ncols_scaled - n0 - 4 * g : 0;
+// (struct Epi224, the branch-free epilogue itself: gemm224_common.h)
+// rows i*16 .. i*16+15 of the wave tile, bias and scale already folded (Epi224::fold_bias): (+ residual) -> bf16 -> LDS staging -> four 16-byte stores
+// per lane group.  This pass and the one in store_tile_224 above are the eight-wave kernel's own: routed through store_pass_224 its bf16
+// instantiations came out with other register and spill counts.
+__device__ __forceinline__ void epi224_pass_folded(const Epi224& e, const GemmArgs& a, const f32x4 (&acc)[7], const uint2 (&r)[7], int i, int m0, int n0, char* stage,
+                                                   int lane) {
+  const int r16 = lane & 15, g = lane >> 4;
+  bf16_t* __restrict__ C = reinterpret_cast<bf16_t*>(a.C);
+#pragma unroll
+  for (int j = 0; j < 7; ++j) {
+    const uint2 rr = e.has_res ? r[j] : make_uint2(0u, 0u);
+    uint2 pk;
+    pk.x = pack_bf16x2(acc[j][0] + bf16_lo(rr.x), acc[j][1] + bf16_hi(rr.x));
+    pk.y = pack_bf16x2(acc[j][2] + bf16_lo(rr.y), acc[j][3] + bf16_hi(rr.y));
+    *reinterpret_cast<uint2*>(stage + r16 * 240 + (j * 16 + 4 * g) * 2) = pk;      // 240-byte rows: 16 B of padding
   }
-  __device__ __forceinline__ void load_bias(float4 (&b)[7]) const {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
-    for (int j = 0; j < 7; ++j) b[j] = *reinterpret_cast<const float4*>(bias_p + j * 16);
-  }
-  __device__ __forceinline__ void load_res(int i, uint2 (&r)[7]) const {       // rows m0 + i*16 + r16 of the wave's tile
-#pragma unroll
-    for (int j = 0; j < 7; ++j) r[j] = *reinterpret_cast<const uint2*>(res_p + (size_t)(i * 16) * res_ld + j * 16);
-  }
-  // acc = (acc + bias) * scale for the whole 64 x 112 wave tile
-  __device__ __forceinline__ void fold_bias(f32x4 (&acc)[4][7], const float4 (&b)[7]) const {
-#pragma unroll
-    for (int j = 0; j < 7; ++j) {
-      const float sc = (j * 16 < ncols_scaled) ? colscale : 1.0f;
-      const float4 bb = has_bias ? b[j] : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        acc[i][j][0] = (acc[i][j][0] + bb.x) * sc;
-        acc[i][j][1] = (acc[i][j][1] + bb.y) * sc;
-        acc[i][j][2] = (acc[i][j][2] + bb.z) * sc;
-        acc[i][j][3] = (acc[i][j][3] + bb.w) * sc;
-      }
+  for (int it = 0; it < 4; ++it) {
+    const int idx = it * 64 + lane;
+    const int row = idx / 14, ch = idx - row * 14;
+    if (idx < 16 * 14) {
+      const uint4 val = *reinterpret_cast<const uint4*>(stage + row * 240 + ch * 16);
+      *reinterpret_cast<uint4*>(C + (size_t)(m0 + i * 16 + row) * a.ldc + n0 + ch * 8) = val;
     }
   }
-  // rows i*16 .. i*16+15 of the wave tile: (+ residual) -> bf16 -> LDS staging -> four 16-byte stores per lane group
-  __device__ __forceinline__ void pass(const GemmArgs& a, const f32x4 (&acc)[7], const uint2 (&r)[7], int i, int m0, int n0, char* stage, int lane) const {
-    const int r16 = lane & 15, g = lane >> 4;
-    bf16_t* __restrict__ C = reinterpret_cast<bf16_t*>(a.C);
-#pragma unroll
-    for (int j = 0; j < 7; ++j) {
-      const uint2 rr = has_res ? r[j] : make_uint2(0u, 0u);
-      uint2 pk;
-      pk.x = pack_bf16x2(acc[j][0] + bf16_lo(rr.x), acc[j][1] + bf16_hi(rr.x));
-      pk.y = pack_bf16x2(acc[j][2] + bf16_lo(rr.y), acc[j][3] + bf16_hi(rr.y));
-      *reinterpret_cast<uint2*>(stage + r16 * 240 + (j * 16 + 4 * g) * 2) = pk;      // 240-byte rows: 16 B of padding
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-      const int idx = it * 64 + lane;
-      const int row = idx / 14, ch = idx - row * 14;
-      if (idx < 16 * 14) {
-        const uint4 val = *reinterpret_cast<const uint4*>(stage + row * 240 + ch * 16);
-        *reinterpret_cast<uint4*>(C + (size_t)(m0 + i * 16 + row) * a.ldc + n0 + ch * 8) = val;
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  }
-};
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
 
 // PERSIST = false: one tile per workgroup.  The workgroup ends right behind its last store instruction, so the stores drain
 // while the CU's next workgroup starts its K loop, and no state of a next tile lives across the epilogue (the persistent form
@@ -254,7 +213,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_224_kernel(const GemmArgs a)
   constexpr int B_OFF = MIDBAR ? 2 * A_BYTES : B_BASE;           // MIDBAR: two A images, THREE B images (the store staging aliases the third)
   char* stage = smem + (MIDBAR ? 2 * A_BYTES + 4 * HT_BYTES : 2 * A_BYTES) + wave_u * 4096;
 
-  const int ntn = a.N / BN224;
+  const int ntn = a.N / G224_BN;
   const int ntm = (a.M + 255) / 256;
   const int nt = ntn * ntm;
   const int kbeg = blockIdx.z * a.ksplit;
@@ -269,27 +228,20 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_224_kernel(const GemmArgs a)
   // XCD gets a contiguous run of tile ids, and ids walk the tile grid in bands of 4 tile-rows, column-major inside a band:
   // the 32 tiles an XCD works on at a time form a 4 x 8 block (4 A panels + 8 B panels per K-step) instead of a
   // 1.3 x 24 strip that streams ALL of the weight matrix through every L2 in every round.
-  auto tile_origin = [&](int t, int& bm0, int& bn0) {
-    const int id = xcd_remap(t, nt);
-    if (a.order == 0) { bm0 = (id / ntn) * 256; bn0 = (id % ntn) * BN224; return; }
-    const int band = id / (4 * ntn), within = id - band * 4 * ntn;
-    const int rows = min(4, ntm - band * 4);
-    bm0 = (band * 4 + within % rows) * 256;
-    bn0 = (within / rows) * BN224;
-  };
+  auto origin = [&](int t, int& bm0, int& bn0) { tile_origin(xcd_remap(t, nt), ntn, ntm, a.order, bm0, bn0); };
   int bm0, bn0;
   // MIDBAR = false: A(kt) lives in A image kt % 3 (`ab`), B(kt) in B image kt & 1;  MIDBAR = true: both in images kt & 1
   auto dmaA = [&](int h, int kt, int ab) {
     dma_half<A_KMAJOR>(A, a.lda, bm0 + h * 128, a.M, kbeg + kt * BK, smem + ab * A_BYTES + h * HT_BYTES, wave_u, lane);
   };
   auto dmaB = [&](int h, int kt, int img) {
-    dma_half<B_KMAJOR>(B, a.ldb, bn0 + h * HN224, a.N, kbeg + kt * BK, smem + B_OFF + (img * 2 + h) * HT_BYTES, wave_u, lane);
+    dma_half<B_KMAJOR>(B, a.ldb, bn0 + h * G224_HN, a.N, kbeg + kt * BK, smem + B_OFF + (img * 2 + h) * HT_BYTES, wave_u, lane);
   };
   auto dmaA1 = [&](int h, int kt, int ab, auto I) {
     dma_half<A_KMAJOR, decltype(I)::value>(A, a.lda, bm0 + h * 128, a.M, kbeg + kt * BK, smem + ab * A_BYTES + h * HT_BYTES, wave_u, lane);
   };
   auto dmaB1 = [&](int h, int kt, int img, auto I) {
-    dma_half<B_KMAJOR, decltype(I)::value>(B, a.ldb, bn0 + h * HN224, a.N, kbeg + kt * BK, smem + B_OFF + (img * 2 + h) * HT_BYTES, wave_u, lane);
+    dma_half<B_KMAJOR, decltype(I)::value>(B, a.ldb, bn0 + h * G224_HN, a.N, kbeg + kt * BK, smem + B_OFF + (img * 2 + h) * HT_BYTES, wave_u, lane);
   };
   // copy instructions per wave and K-tile: 4 for A, 4 for B.  Issue order matters for the counted waits (in-order counter).
   auto prologue = [&]() {
@@ -309,7 +261,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_224_kernel(const GemmArgs a)
 
   int t = blockIdx.x;
   if (t >= nt) return;
-  tile_origin(t, bm0, bn0);
+  origin(t, bm0, bn0);
   auto wait_first_tile = [&]() {                 // K-tile 0 has landed: everything but the copies of K-tile 1
     if (nk > 1) { if constexpr (MIDBAR) asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -341,6 +293,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_224_kernel(const GemmArgs a)
       // twice for the two image parities) does not fit next to 112 accumulators and 88 fragment registers: it spilled fragment
       // registers whose LDS data had not arrived yet.
       const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+      // (kmajor_frag_offsets of gemm224_common.h, written out: through the helper the NN bf16 kernel came out with another VGPR count)
       unsigned lk[2];
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) lk[ks] = r16 * 128 + (((ks * 4 + g) ^ ((r16 >> 1) & 7)) << 4);
@@ -618,7 +571,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_224_kernel(const GemmArgs a)
     if (a.stamps && lane == 0 && round == 0)
       for (int i = 0; i < 8; ++i) a.stamps[((size_t)(blockIdx.x + gridDim.x * blockIdx.z) * 8 + wave_u) * 8 + i] = pacc[i];
 #endif
-    const int m0 = bm0 + wm * 64, n0 = bn0 + wn * HN224;
+    const int m0 = bm0 + wm * 64, n0 = bn0 + wn * G224_HN;
     bool fast = false;
     if constexpr (sizeof(TC) == 2 && !PERSIST) fast = (a.variant != 1) && epi224_fast_ok(a, bm0);
     t += gridDim.x;
@@ -637,18 +590,18 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_224_kernel(const GemmArgs a)
       e.fold_bias(acc, bias);
       e.load_res(1, r1);
       e.load_res(2, r2);
-      e.pass(a, acc[0], r0, 0, m0, n0, stage, lane);
+      epi224_pass_folded(e, a, acc[0], r0, 0, m0, n0, stage, lane);
       e.load_res(3, r0);                                               // r0 is free again
       asm volatile("s_waitcnt vmcnt(11)" ::: "memory");                // res1, res2: older than stores p0 (4) + res3 (7)
-      e.pass(a, acc[1], r1, 1, m0, n0, stage, lane);
-      e.pass(a, acc[2], r2, 2, m0, n0, stage, lane);
+      epi224_pass_folded(e, a, acc[1], r1, 1, m0, n0, stage, lane);
+      epi224_pass_folded(e, a, acc[2], r2, 2, m0, n0, stage, lane);
       asm volatile("s_waitcnt vmcnt(8)" ::: "memory");                 // res3: older than stores p1, p2
-      e.pass(a, acc[3], r0, 3, m0, n0, stage, lane);
+      epi224_pass_folded(e, a, acc[3], r0, 3, m0, n0, stage, lane);
       STAMP(3);
       break;                                                           // the stores drain behind the workgroup's end
     } else {
       if (more) {
-        tile_origin(t, bm0, bn0);
+        origin(t, bm0, bn0);
         prologue();
       }
       STAMP(2);
@@ -667,7 +620,7 @@ template <int LAYOUT, typename TC, bool PERSIST, bool MIDBAR>
 static int launch_one_p(const GemmArgs& a, int splits, hipStream_t st) {
   auto k = gemm_bf16_224_kernel<LAYOUT, TC, PERSIST, MIDBAR>;
   if (int rc = mts_dyn_lds(k, LDS_TOTAL, "gemm224")) return rc;
-  const int nt = ceil_div(a.M, 256) * (a.N / BN224);
+  const int nt = ceil_div(a.M, 256) * (a.N / G224_BN);
   const int gx = (PERSIST && splits == 1) ? std::min(nt, 256) : nt;
 #ifdef MTS_GEMM_STAMPS
   GemmArgs b = a;

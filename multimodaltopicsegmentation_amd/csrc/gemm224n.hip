@@ -15,25 +15,19 @@
 // bitwise those of gemm_bf16_224_kernel<NN> (tests/test_gpu_kernels.py::test_gemm_224n_matches_the_eight_wave_kernel_bitwise).
 #include <algorithm>
 #include <type_traits>
-#include "gemm_common.h"
+#include "gemm224_common.h"
 
 #define N_A_BYTES 32768                       // 256 rows x 128 B (K-major)
 #define N_B_BYTES 32768                       // 2 k-steps x 2 halves x [32 k][256 B]
 #define N_STAGE (N_A_BYTES + N_B_BYTES)
 #define N_EPI (2 * N_STAGE)                   // the epilogue's output staging: 4 x 4 KiB behind the stages (the stages take the residual tile)
 #define N_LDS (2 * N_STAGE + 16384)           // 144 KiB
-#define N_BN 224
-#define N_HN 112
-
-typedef __attribute__((address_space(3))) void n_dlptr;
-
-struct NFrag { s16x4 lo, hi; };
 
 // (free function templates, not generic lambdas: clang rejects inline-asm operands that name variables captured by a generic lambda)
 // read operation R (0..21) of k-step KS: 2 j, 2 j + 1 = the halves of B fragment j; 14 + i = A fragment i.  sA / sB: stage base (+ the wave's
 // A rows) and stage base + B region + k-step + the wave's half image
 template <int KS, int R>
-__device__ __forceinline__ void n_rd(s16x8 (&fa)[2][8], NFrag (&fb)[2][7], unsigned sA, unsigned sB, const unsigned (&lk)[2], const unsigned (&ax)[7]) {
+__device__ __forceinline__ void n_rd(s16x8 (&fa)[2][8], frag_raw (&fb)[2][7], unsigned sA, unsigned sB, const unsigned (&lk)[2], const unsigned (&ax)[7]) {
   if constexpr (R < 14) {
     constexpr int j = R >> 1;
     const unsigned ad = ax[j] + sB;
@@ -46,14 +40,11 @@ __device__ __forceinline__ void n_rd(s16x8 (&fa)[2][8], NFrag (&fb)[2][7], unsig
 }
 // block N of a K-tile: A fragment N & 7 of k-step N >> 3 x the 7 B fragments (joined once per k-step, in its first block)
 template <int N>
-__device__ __forceinline__ void n_block(f32x4 (&acc)[8][7], s16x8 (&fa)[2][8], NFrag (&fb)[2][7], bf16x8 (&ob)[7]) {
+__device__ __forceinline__ void n_block(f32x4 (&acc)[8][7], s16x8 (&fa)[2][8], frag_raw (&fb)[2][7], bf16x8 (&ob)[7]) {
   constexpr int ks = N >> 3, i = N & 7;
   if constexpr (i == 0) {
 #pragma unroll
-    for (int j = 0; j < 7; ++j) {
-      asm volatile("" : "+v"(fb[ks][j].lo), "+v"(fb[ks][j].hi));
-      ob[j] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(fb[ks][j].lo, fb[ks][j].hi, 0, 1, 2, 3, 4, 5, 6, 7));
-    }
+    for (int j = 0; j < 7; ++j) ob[j] = frag_finish(fb[ks][j]);
   }
   asm volatile("" : "+v"(fa[ks][i]));
   const bf16x8 va = __builtin_bit_cast(bf16x8, fa[ks][i]);
@@ -67,44 +58,24 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_224n_kernel(const GemmArgs a
   const int lane = tid & 63;
   const int wave_u = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave_u >> 1, wn = wave_u & 1;
-  const int r16 = lane & 15, g = lane >> 4, q = r16 >> 2, p = r16 & 3;
-  const int ntn = a.N / N_BN, ntm = a.M / 256, nt = ntn * ntm;
+  const int r16 = lane & 15, g = lane >> 4;
+  const int ntn = a.N / G224_BN, ntm = a.M / 256, nt = ntn * ntm;
   const int nk = a.K / BK;
   const bf16_t* __restrict__ A = reinterpret_cast<const bf16_t*>(a.A);
   const bf16_t* __restrict__ B = reinterpret_cast<const bf16_t*>(a.B);
   int bm0, bn0;
-  {
-    const int id = xcd_remap(blockIdx.x, nt);
-    if (a.order == 0) { bm0 = (id / ntn) * 256; bn0 = (id % ntn) * N_BN; }
-    else {
-      const int band = id / (4 * ntn), within = id - band * 4 * ntn;
-      const int rows = min(4, ntm - band * 4);
-      bm0 = (band * 4 + within % rows) * 256;
-      bn0 = (within / rows) * N_BN;
-    }
-  }
-  // ---- copies.  A: 32 pieces of 1 KiB (8 rows x 128 B) per K-tile, 8 per wave, as in gemm_bf16_224d_kernel (lane (row8, pos) fetches chunk
-  // pos ^ key(row) of its row: one of two lane offsets by the parity of the piece).  B: per k-step two half images, each 8 pieces of 4 k-rows x
-  // 256 B; lane (lr = lane >> 4, c16 = lane & 15) fills k-row lr, 32-B slot c16 >> 1, half c16 & 1, and slot s of k-row r holds source column
-  // block s ^ key(r), key(r) = (r & 3) | (((r >> 3) & 1) << 2) (gemm_common.h strided_off): r = 4 piece + lr, so the key is lr | (bit 1 of the
-  // piece number << 2) -- two lane offsets.  A half image holds 112 used columns of 128: the lanes of the unused 16 fetch 16 columns further
-  // left (nobody reads what they bring).  Wave w copies pieces 4 (w & 1) .. + 3 of half image w >> 1 of both k-steps: 8 copies.
-  const int row8 = lane >> 3, pos = lane & 7;
-  const unsigned keyE = (unsigned)((row8 >> 1) & 7), keyO = (unsigned)(((row8 >> 1) + 4) & 7);
-  const unsigned voA[2] = {(unsigned)(row8 * a.lda + (int)((pos ^ keyE) * 8)) * 2u, (unsigned)(row8 * a.lda + (int)((pos ^ keyO) * 8)) * 2u};
-  const int lr = lane >> 4, c16 = lane & 15;
-  unsigned voB[2];
-#pragma unroll
-  for (int par = 0; par < 2; ++par) {
-    const int key = lr | (par << 2);
-    const int col = (((c16 >> 1) ^ key) << 4) + ((c16 & 1) << 3);
-    voB[par] = (unsigned)(lr * a.ldb + (col >= N_HN ? col - 16 : col)) * 2u;
-  }
-  const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)(A + (size_t)bm0 * a.lda), 0, 0x7ffffff0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void*)(B + bn0), 0, 0x7ffffff0, 0x00020000);
+  tile_origin(xcd_remap(blockIdx.x, nt), ntn, ntm, a.order, bm0, bn0);
+  // ---- copies.  A: 32 pieces of 1 KiB (8 rows x 128 B) per K-tile, 8 per wave, as in gemm_bf16_224d_kernel (kmajor_copy_offsets).  B: per
+  // k-step two half images of 112 used columns, each 8 pieces of 4 k-rows x 256 B (strided_copy_offsets, clipped); wave w copies pieces
+  // 4 (w & 1) .. + 3 of half image w >> 1 of both k-steps: 8 copies.  Either way a copy's lane offset is one of two, by the parity of the piece.
+  unsigned voA[2], voB[2];
+  kmajor_copy_offsets(lane, a.lda, voA);
+  strided_copy_offsets(lane, a.ldb, G224_HN, voB);
+  const __amdgpu_buffer_rsrc_t rsA = make_rsrc(A + (size_t)bm0 * a.lda);
+  const __amdgpu_buffer_rsrc_t rsB = make_rsrc(B + bn0);
   const int rowsA = 16 * a.lda;                                    // bytes per 8 rows of A
   const int h_w = wave_u >> 1, pi0 = (wave_u & 1) * 4;
-  const int sB0 = (4 * pi0 * a.ldb + h_w * N_HN) * 2;
+  const int sB0 = (4 * pi0 * a.ldb + h_w * G224_HN) * 2;
   const int rowB4 = 8 * a.ldb, stepB = 64 * a.ldb, tileB = 128 * a.ldb;   // bytes per 4 / 32 / 64 k-rows of B
   // copy number c (0..15) of this wave for K-tile kt into stage st: 0..7 = A piece 8 wave + c; 8..15 = B: k-step (c - 8) >> 2, piece pi0 + (c & 3)
   auto copy1 = [&](auto C, int kt, int st) {
@@ -112,28 +83,24 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_224n_kernel(const GemmArgs a
     char* dst0 = smem + st * N_STAGE;
     if constexpr (c < 8) {
       const int piece = wave_u * 8 + c;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (n_dlptr*)(dst0 + piece * 1024), 16, voA[c & 1], piece * rowsA + kt * (BK * 2), 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (dlptr_t*)(dst0 + piece * 1024), 16, voA[c & 1], piece * rowsA + kt * (BK * 2), 0, 0);
     } else {
       constexpr int ks = (c - 8) >> 2, cc = c & 3;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (n_dlptr*)(dst0 + N_A_BYTES + ks * 16384 + h_w * 8192 + (pi0 + cc) * 1024), 16, voB[(cc >> 1) & 1],
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (dlptr_t*)(dst0 + N_A_BYTES + ks * 16384 + h_w * 8192 + (pi0 + cc) * 1024), 16, voB[(cc >> 1) & 1],
                                                sB0 + cc * rowB4 + ks * stepB + kt * tileB, 0, 0);
     }
   };
   // ---- fragment reads.  A: row r16 of the 16-row block, 16-byte chunk ks * 4 + g (K-major swizzle).  B: X[k = 8 g + q (+ 4), column block j,
   // columns 4 p ..] through two transposing reads (gemm_common.h frag_strided)
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-  unsigned lk[2];
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks) lk[ks] = r16 * 128 + (((ks * 4 + g) ^ ((r16 >> 1) & 7)) << 4);
-  const unsigned sx = (unsigned)((8 * g + q) * 256 + 8 * p + ((q | ((g & 1) << 2)) << 5));
-  unsigned ax[7];
-#pragma unroll
-  for (int c = 0; c < 7; ++c) ax[c] = sx ^ (unsigned)(c << 5);
+  unsigned lk[2], ax[7];
+  kmajor_frag_offsets(r16, g, lk);
+  strided_frag_offsets(r16, g, 0u, ax);
   const unsigned fA = lds0 + wm * 16384;
   const unsigned fB = lds0 + wn * 8192;
 
   s16x8 fa[2][8];
-  NFrag fb[2][7];
+  frag_raw fb[2][7];
   bf16x8 ob[7];
   f32x4 acc[8][7];
 #pragma unroll
@@ -147,26 +114,22 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_224n_kernel(const GemmArgs a
 #define CP16(KT_, ST_) CP(0, KT_, ST_); CP(1, KT_, ST_); CP(2, KT_, ST_); CP(3, KT_, ST_); CP(4, KT_, ST_); CP(5, KT_, ST_); CP(6, KT_, ST_); CP(7, KT_, ST_); \
                        CP(8, KT_, ST_); CP(9, KT_, ST_); CP(10, KT_, ST_); CP(11, KT_, ST_); CP(12, KT_, ST_); CP(13, KT_, ST_); CP(14, KT_, ST_); CP(15, KT_, ST_)
   // the epilogue's bias (7 x 16 bytes per lane) is fetched ahead of every copy (a data gradient rarely has one)
-  const int m0 = bm0 + wm * 128, n0 = bn0 + wn * N_HN;
-  const bool has_bias = (a.epi & MTS_EPI_BIAS) != 0, has_res = (a.epi & MTS_EPI_RESIDUAL) != 0;
-  const float* bias_p = has_bias ? a.bias + n0 + 4 * g : reinterpret_cast<const float*>(a.A) + 4 * g;
+  const int m0 = bm0 + wm * 128, n0 = bn0 + wn * G224_HN;
+  Epi224 e;
+  e.init_loads(a, m0, n0, true, r16, g);
+  const bool has_res = e.has_res;
   float4 bias[7];
-#pragma unroll
-  for (int j = 0; j < 7; ++j) bias[j] = *reinterpret_cast<const float4*>(bias_p + j * 16);
+  e.load_bias(bias);
   // ---- the residual tile goes through the LDS.  Fetched into registers in the epilogue it is 56 loads per lane and a memory round trip per tile
   // with nothing to hide it (one tile per workgroup): 278 against 246 us on the Q|K|V data gradient.  The two stages are dead a K-tile apart at the
   // end of the K loop: the wave's rows 0..63 (x 112 columns = 14 chunks of 16 B per row) are copied into the stage of K-tile nk - 2 behind that
   // K-tile's barrier 2, rows 64..127 into the stage of K-tile nk - 1 behind its last fragment read -- 16 LDS-DMA each, four rows per copy (lane =
   // (row in four, chunk): 56 of 64 lanes), 16 KiB per wave and half; the epilogue reads 8 bytes per (row, 16-column block) back.
-  const __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc(
-      has_res ? (void*)(reinterpret_cast<const bf16_t*>(a.residual) + (size_t)m0 * a.ldr + n0) : (void*)A, 0, 0x7ffffff0, 0x00020000);
-  const unsigned voR = (unsigned)((lane / 14) * a.ldr + (lane % 14) * 8) * 2u;
-  const int rowR4 = 8 * a.ldr;                                     // bytes per 4 rows of the residual
+  // (ResidualViaLds, gemm224_common.h)
+  ResidualViaLds rv;
+  rv.init(a, has_res, m0, n0, lane);
   // copy c (0..15) of half h: rows 64 h + 4 c .. + 3 -> stage st, 16 KiB of this wave
-  auto res_copy = [&](int c, int h, int st) {
-    if (lane < 56)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsR, (n_dlptr*)(smem + st * N_STAGE + wave_u * 16384 + c * 1024), 16, voR, (h * 16 + c) * rowR4, 0, 0);
-  };
+  auto res_copy = [&](int c, int h, int st) { rv.copy(c, h, smem + st * N_STAGE + wave_u * 16384, lane); };
   // ---- prologue: K-tiles 0 and 1 -> stages 0 and 1; the fragments of K-tile 0 / k-step 0 requested ------------------------------------------
   CP16(0, 0);
   CP16(1, 1);
@@ -243,45 +206,19 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_224n_kernel(const GemmArgs a
   const int stA = (nk - 2) & 1;                              // the stage that took the first half of the residual
   if (has_res) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");     // the first half has landed (in-order counter): the second half's 16 copies may still fly
   else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  const float colscale = (a.epi & MTS_EPI_COLSCALE) ? a.colscale : 1.0f;
-  const int nsc = (a.epi & MTS_EPI_COLSCALE) ? a.ncols_scaled - n0 - 4 * g : 0;
-  bf16_t* __restrict__ C = reinterpret_cast<bf16_t*>(a.C);
+  e.init_scale(a, n0, g);
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     // (younger than the second half's copies are the 16 store instructions of groups 0..3)
     if (i == 4 && has_res) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
     uint2 res[7];
     if (has_res) {
-      // row i * 16 + r16 of the wave's 128 = row (i & 3) * 16 + r16 of its half: copy (row >> 2), lane slot (row & 3) * 14 + chunk
-      const int rr = (i & 3) * 16 + r16;
-      const char* rp = smem + ((i < 4) ? stA : (stA ^ 1)) * N_STAGE + wave_u * 16384 + (rr >> 2) * 1024 + ((rr & 3) * 14 + (g >> 1)) * 16 + (g & 1) * 8;
-#pragma unroll
-      for (int j = 0; j < 7; ++j) res[j] = *reinterpret_cast<const uint2*>(rp + j * 32);
+      ResidualViaLds::read(i, smem + ((i < 4) ? stA : (stA ^ 1)) * N_STAGE + wave_u * 16384, r16, g, res);
     } else {
 #pragma unroll
       for (int j = 0; j < 7; ++j) res[j] = make_uint2(0u, 0u);
     }
-#pragma unroll
-    for (int j = 0; j < 7; ++j) {
-      const float sc = (j * 16 < nsc) ? colscale : 1.0f;
-      const float4 bb = has_bias ? bias[j] : make_float4(0.f, 0.f, 0.f, 0.f);
-      const uint2 rr2 = has_res ? res[j] : make_uint2(0u, 0u);
-      uint2 pk;
-      pk.x = pack_bf16x2((acc[i][j][0] + bb.x) * sc + bf16_lo(rr2.x), (acc[i][j][1] + bb.y) * sc + bf16_hi(rr2.x));
-      pk.y = pack_bf16x2((acc[i][j][2] + bb.z) * sc + bf16_lo(rr2.y), (acc[i][j][3] + bb.w) * sc + bf16_hi(rr2.y));
-      *reinterpret_cast<uint2*>(stage + r16 * 240 + (j * 16 + 4 * g) * 2) = pk;
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-      const int idx = it * 64 + lane;
-      const int row = idx / 14, chn = idx - row * 14;
-      if (idx < 16 * 14) {
-        const uint4 val = *reinterpret_cast<const uint4*>(stage + row * 240 + chn * 16);
-        *reinterpret_cast<uint4*>(C + (size_t)(m0 + i * 16 + row) * a.ldc + n0 + chn * 8) = val;
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    e.pass(a, acc[i], bias, res, i, m0, n0, stage, lane, r16, g);
   }
 }
 
@@ -293,15 +230,9 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_224n_kernel(const GemmArgs a
 bool mts_gemm224n_applies(const GemmArgs& a, int layout, bool c_is_f32, int splits) {
   if (c_is_f32 || splits != 1 || layout != MTS_NN) return false;
   if ((a.epi & MTS_EPI_RESIDUAL) && a.variant == 11) return false;
-  const unsigned simple = MTS_EPI_BIAS | MTS_EPI_COLSCALE | MTS_EPI_RESIDUAL;
-  const size_t spanB = ((size_t)a.K + 64) * a.ldb * 2;     // byte offsets of the B copies stay below 2^31
-  return !a.slab && (a.epi & ~simple) == 0 && (a.M % 256 == 0) && (a.N % N_BN == 0) && (a.K % BK == 0) && a.K >= 2 * BK && a.ksplit == a.K &&
-         (a.ldc % 8 == 0) && (((uintptr_t)a.C & 15) == 0) && (a.lda % 8 == 0) && (a.ldb % 8 == 0) && (((uintptr_t)a.A & 15) == 0) &&
-         (((uintptr_t)a.B & 15) == 0) && spanB < 0x7ff00000u && (size_t)256 * a.lda * 2 + (size_t)a.K * 2 < 0x7ff00000u &&
-         (!(a.epi & MTS_EPI_COLSCALE) || a.ncols_scaled % 4 == 0) &&
-         // (the residual tile is copied to the LDS in 16-byte pieces)
-         (!(a.epi & MTS_EPI_RESIDUAL) || (a.ldr % 8 == 0 && ((uintptr_t)a.residual & 15) == 0)) &&
-         (!(a.epi & MTS_EPI_BIAS) || ((uintptr_t)a.bias & 15) == 0);
+  // (the residual tile is copied to the LDS in 16-byte pieces)
+  return g224_simple_epi_ok(a, 16) && g224_c_bf16_ok(a) && (a.M % 256 == 0) && (a.N % G224_BN == 0) && (a.K % BK == 0) && a.K >= 2 * BK && a.ksplit == a.K &&
+         g224_operand_ok(a.A, a.lda, g224_kmajor_span(256, a.lda, a.K)) && g224_operand_ok(a.B, a.ldb, g224_strided_span(a.K, a.ldb));
 }
 
 // called from mts_launch_gemm224 (gemm224.hip); -1: shape / epilogue not covered here
@@ -309,7 +240,7 @@ int mts_launch_gemm224n(const GemmArgs& a, int layout, bool c_is_f32, int splits
   if (!mts_gemm224n_applies(a, layout, c_is_f32, splits)) return -1;
   auto k = gemm_bf16_224n_kernel;
   if (int rc = mts_dyn_lds(k, N_LDS, "gemm224n")) return rc;
-  const int nt = (a.M / 256) * (a.N / N_BN);
+  const int nt = (a.M / 256) * (a.N / G224_BN);
   hipLaunchKernelGGL(k, dim3(nt), dim3(256), N_LDS, st, a);
   return MTS_OK;
 }

@@ -18,42 +18,13 @@
 // gemm_bf16_224d_kernel (tests/test_gpu_kernels.py::test_gemm_224_barrier_schedules_agree_bitwise, variants 0 / 9).
 #include <algorithm>
 #include <type_traits>
-#include "gemm_common.h"
+#include "gemm224_common.h"
 
 #define P_A_BYTES 32768                       // 256 rows x 128 B (K-major)
 #define P_STAGE 65536                         // A image | B image (224 rows x 128 B = 28 KiB used)
 #define P_EPI (2 * P_STAGE)                   // store staging: 4 waves x 4 KiB
 #define P_BIAS (P_EPI + 16384)                // the tile's bias row: 224 floats
 #define P_LDS (P_BIAS + 1024)
-#define P_BN 224
-#define P_HN 112
-
-typedef __attribute__((address_space(3))) void p_dlptr;
-
-// request R (0..14) of k-step KS: 0..6 = B fragment R, 7..14 = A fragment R - 7 (fA / fB: the wave's image bases incl. the stage)
-template <int KS, int R>
-__device__ __forceinline__ void p_rd(s16x8 (&fa)[2][8], s16x8 (&fb)[2][7], unsigned fA, unsigned fB, const unsigned (&lk)[2]) {
-  if constexpr (R < 7) {
-    const unsigned ad = fB + lk[KS];
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(fb[KS][R]) : "v"(ad), "n"(R * 2048));
-  } else {
-    const unsigned ad = fA + lk[KS];
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(fa[KS][R - 7]) : "v"(ad), "n"((R - 7) * 2048));
-  }
-}
-// block N = 8 ks + i: A fragment i of k-step ks x the 7 B fragments.  ZERO: the accumulators of row block i start here (C = 0)
-template <int N, bool ZERO>
-__device__ __forceinline__ void p_block(f32x4 (&acc)[8][7], s16x8 (&fa)[2][8], s16x8 (&fb)[2][7]) {
-  constexpr int ks = N >> 3, i = N & 7;
-  asm volatile("" : "+v"(fa[ks][i]));
-  const bf16x8 va = __builtin_bit_cast(bf16x8, fa[ks][i]);
-#pragma unroll
-  for (int j = 0; j < 7; ++j) {
-    asm volatile("" : "+v"(fb[ks][j]));
-    if constexpr (ZERO) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fb[ks][j]), va, (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-    else acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fb[ks][j]), va, acc[i][j], 0, 0, 0);
-  }
-}
 
 __global__ __launch_bounds__(256, 1) void gemm_bf16_224p_kernel(const GemmArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -62,7 +33,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_224p_kernel(const GemmArgs a
   const int wave_u = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave_u >> 1, wn = wave_u & 1;
   const int r16 = lane & 15, g = lane >> 4;
-  const int ntn = a.N / P_BN, ntm = a.M / 256, nt = ntn * ntm;
+  const int ntn = a.N / G224_BN, ntm = a.M / 256, nt = ntn * ntm;
   const int nk = a.K / BK;
   const bf16_t* __restrict__ A = reinterpret_cast<const bf16_t*>(a.A);
   const bf16_t* __restrict__ B = reinterpret_cast<const bf16_t*>(a.B);
@@ -71,35 +42,26 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_224p_kernel(const GemmArgs a
   const int G = gridDim.x, xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
   const int wx = (G - xcd + 7) >> 3;                          // workgroups of this launch on my XCD
   const int first = xcd_remap(xcd, nt), cnt = (nt >> 3) + (xcd < (nt & 7) ? 1 : 0);   // block id xcd heads the XCD's run
-  auto origin = [&](int j, int& bm0, int& bn0) {              // j: index inside my XCD's run
-    const int id = first + j;
-    if (a.order == 0) { bm0 = (id / ntn) * 256; bn0 = (id % ntn) * P_BN; return; }
-    const int band = id / (4 * ntn), within = id - band * 4 * ntn;
-    const int rows = min(4, ntm - band * 4);
-    bm0 = (band * 4 + within % rows) * 256;
-    bn0 = (within / rows) * P_BN;
-  };
+  auto origin = [&](int j, int& bm0, int& bn0) { tile_origin(first + j, ntn, ntm, a.order, bm0, bn0); };   // j: index inside my XCD's run
   int j = idx;
   if (j >= cnt) return;
 
   // ---- copies: 32 A pieces + 28 B pieces of 1 KiB (8 rows x 128 B) per K-tile, 8 + 7 per wave; the K-major swizzle on the SOURCE side (two lane
   // offsets by the parity of the piece), everything else of a copy's address scalar (gemm_bf16_224d_kernel)
-  const int row8 = lane >> 3, pos = lane & 7;
-  const unsigned keyE = (unsigned)((row8 >> 1) & 7), keyO = (unsigned)(((row8 >> 1) + 4) & 7);
-  const unsigned voA[2] = {(unsigned)(row8 * a.lda + (int)((pos ^ keyE) * 8)) * 2u, (unsigned)(row8 * a.lda + (int)((pos ^ keyO) * 8)) * 2u};
-  const unsigned voB[2] = {(unsigned)(row8 * a.ldb + (int)((pos ^ keyE) * 8)) * 2u, (unsigned)(row8 * a.ldb + (int)((pos ^ keyO) * 8)) * 2u};
+  unsigned voA[2], voB[2];
+  kmajor_copy_offsets(lane, a.lda, voA);
+  kmajor_copy_offsets(lane, a.ldb, voB);
   const int rowsA = 16 * a.lda, rowsB = 16 * a.ldb;          // bytes per 8 rows
-  auto rsrc_of = [&](const bf16_t* p) { return __builtin_amdgcn_make_buffer_rsrc((void*)p, 0, 0x7ffffff0, 0x00020000); };
   // copy c (0..14) of this wave for K-tile kt of the tile whose resources are (ra, rb), into stage st
   auto copy1 = [&](auto C, const __amdgpu_buffer_rsrc_t& ra, const __amdgpu_buffer_rsrc_t& rb, int kt, int st) {
     constexpr int c = decltype(C)::value;
     char* dst0 = smem + st * P_STAGE;
     if constexpr (c < 8) {
       const int piece = wave_u * 8 + c;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (p_dlptr*)(dst0 + piece * 1024), 16, voA[c & 1], piece * rowsA + kt * (BK * 2), 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (dlptr_t*)(dst0 + piece * 1024), 16, voA[c & 1], piece * rowsA + kt * (BK * 2), 0, 0);
     } else {
       const int piece = wave_u * 7 + (c - 8);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (p_dlptr*)(dst0 + P_A_BYTES + piece * 1024), 16, voB[piece & 1], piece * rowsB + kt * (BK * 2), 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (dlptr_t*)(dst0 + P_A_BYTES + piece * 1024), 16, voB[piece & 1], piece * rowsB + kt * (BK * 2), 0, 0);
     }
   };
   const bool has_bias = (a.epi & MTS_EPI_BIAS) != 0, has_res = (a.epi & MTS_EPI_RESIDUAL) != 0;
@@ -107,25 +69,26 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_224p_kernel(const GemmArgs a
   const unsigned voBias = (unsigned)min(lane, 55) * 16u;
   auto copy_bias = [&](int bn0) {
     if (has_bias && wave_u == 0)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(__builtin_amdgcn_make_buffer_rsrc((void*)(a.bias + bn0), 0, 0x7ffffff0, 0x00020000),
-                                               (p_dlptr*)(smem + P_BIAS), 16, voBias, 0, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(make_rsrc(a.bias + bn0), (dlptr_t*)(smem + P_BIAS), 16, voBias, 0, 0, 0);
   };
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+  // (kmajor_frag_offsets, and below Epi224 / store_pass_224 of gemm224_common.h, written out: this kernel spills scalars in its K loop, and through
+  // the helpers it came out with other register and spill counts)
   unsigned lk[2];
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks) lk[ks] = r16 * 128 + (((ks * 4 + g) ^ ((r16 >> 1) & 7)) << 4);
   const unsigned fA = lds0 + wm * 16384;
-  const unsigned fB = lds0 + P_A_BYTES + wn * (P_HN * 128);
+  const unsigned fB = lds0 + P_A_BYTES + wn * (G224_HN * 128);
 
   s16x8 fa[2][8], fb[2][7];
   f32x4 acc[8][7];
 
-#define PBLOCK(N_, Z_) do { __builtin_amdgcn_sched_barrier(0); p_block<N_, Z_>(acc, fa, fb); __builtin_amdgcn_sched_barrier(0); } while (0)
-#define PRD(ST_, KS_, R_) p_rd<KS_, R_>(fa, fb, fA + (ST_) * P_STAGE, fB + (ST_) * P_STAGE, lk)
+#define PBLOCK(N_, Z_) kmajor_block<N_, Z_>(acc, fa, fb)
+#define PRD(ST_, KS_, R_) kmajor_rd<KS_, R_>(fa, fb, fA + (ST_) * P_STAGE, fB + (ST_) * P_STAGE, lk)
 #define PCP(C_, RA_, RB_, KT_, ST_) copy1(std::integral_constant<int, C_>{}, RA_, RB_, KT_, ST_)
   int bm0, bn0;
   origin(j, bm0, bn0);
-  __amdgpu_buffer_rsrc_t rsA = rsrc_of(A + (size_t)bm0 * a.lda), rsB = rsrc_of(B + (size_t)bn0 * a.ldb);
+  __amdgpu_buffer_rsrc_t rsA = make_rsrc(A + (size_t)bm0 * a.lda), rsB = make_rsrc(B + (size_t)bn0 * a.ldb);
   // ---- prologue of the FIRST tile: K-tiles 0 and 1 -> stages 0 and 1, its bias row, the fragments of K-tile 0 / k-step 0 -----------------------
   PCP(0, rsA, rsB, 0, 0); PCP(1, rsA, rsB, 0, 0); PCP(2, rsA, rsB, 0, 0); PCP(3, rsA, rsB, 0, 0); PCP(4, rsA, rsB, 0, 0); PCP(5, rsA, rsB, 0, 0);
   PCP(6, rsA, rsB, 0, 0); PCP(7, rsA, rsB, 0, 0); PCP(8, rsA, rsB, 0, 0); PCP(9, rsA, rsB, 0, 0); PCP(10, rsA, rsB, 0, 0); PCP(11, rsA, rsB, 0, 0);
@@ -143,11 +106,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_224p_kernel(const GemmArgs a
   auto ktile = [&](int kt, auto ZERO, auto NXT, auto CPY, const __amdgpu_buffer_rsrc_t& ra, const __amdgpu_buffer_rsrc_t& rb, int ckt) {
     constexpr bool zero = decltype(ZERO)::value, nxt = decltype(NXT)::value, cpy = decltype(CPY)::value;
     const int st = kt & 1;
-#define KA(n)                                                               \
-    lgkm_wait<(7 - (n)) + 2 * (n)>();                                       \
-    PBLOCK(n, zero);                                                        \
-    if constexpr (2 * (n) < 15) PRD(st, 1, (2 * (n) < 15 ? 2 * (n) : 0));       \
-    if constexpr (2 * (n) + 1 < 15) PRD(st, 1, (2 * (n) + 1 < 15 ? 2 * (n) + 1 : 0));
+#define KA(n) kmajor_step0<n, zero, P_STAGE>(acc, fa, fb, fA, fB, st, lk);
     KA(0) KA(1) KA(2) KA(3) KA(4) KA(5) KA(6) KA(7)
 #undef KA
     lgkm_wait<0>();                                         // every fragment of this K-tile is in my registers
@@ -187,8 +146,8 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_224p_kernel(const GemmArgs a
     const bool more = jn < cnt;
     int bm0n, bn0n;
     origin(more ? jn : j, bm0n, bn0n);
-    const __amdgpu_buffer_rsrc_t rsAn = rsrc_of(A + (size_t)bm0n * a.lda), rsBn = rsrc_of(B + (size_t)bn0n * a.ldb);
-    const int m0 = bm0 + wm * 128, n0 = bn0 + wn * P_HN;
+    const __amdgpu_buffer_rsrc_t rsAn = make_rsrc(A + (size_t)bm0n * a.lda), rsBn = make_rsrc(B + (size_t)bn0n * a.ldb);
+    const int m0 = bm0 + wm * 128, n0 = bn0 + wn * G224_HN;
 
     ktile(0, T{}, T{}, T{}, rsA, rsB, 2);
     int kt = 1;
@@ -209,7 +168,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_224p_kernel(const GemmArgs a
     // read, i.e. before the data has arrived)
     f32x4 bias[7];
     {
-      const unsigned bad = lds0 + P_BIAS + (unsigned)(wn * P_HN + 4 * g) * 4u;
+      const unsigned bad = lds0 + P_BIAS + (unsigned)(wn * G224_HN + 4 * g) * 4u;
 #pragma unroll
       for (int jj = 0; jj < 7; ++jj) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bias[jj]) : "v"(bad), "n"(jj * 64));
     }
@@ -275,18 +234,13 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_224p_kernel(const GemmArgs a
 // called from mts_launch_gemm224 (gemm224.hip); -1: shape / epilogue not covered here
 int mts_launch_gemm224p(const GemmArgs& a, int layout, bool c_is_f32, int splits, hipStream_t st) {
   if (c_is_f32 || splits != 1 || layout != MTS_NT) return -1;
-  const unsigned simple = MTS_EPI_BIAS | MTS_EPI_COLSCALE | MTS_EPI_RESIDUAL;
-  const size_t spanA = (size_t)256 * a.lda * 2 + (size_t)a.K * 2, spanB = (size_t)224 * a.ldb * 2 + (size_t)a.K * 2;    // byte offsets inside a tile's panels
-  const bool ok = !a.slab && (a.epi & ~simple) == 0 && (a.M % 256 == 0) && (a.N % P_BN == 0) && (a.K % (2 * BK) == 0) && a.K >= 4 * BK && a.ksplit == a.K &&
-                  (a.ldc % 8 == 0) && (((uintptr_t)a.C & 15) == 0) && (a.lda % 8 == 0) && (a.ldb % 8 == 0) && (((uintptr_t)a.A & 15) == 0) &&
-                  (((uintptr_t)a.B & 15) == 0) && spanA < 0x7ff00000u && spanB < 0x7ff00000u &&
-                  (!(a.epi & MTS_EPI_COLSCALE) || a.ncols_scaled % 4 == 0) &&
-                  (!(a.epi & MTS_EPI_RESIDUAL) || (a.ldr % 4 == 0 && ((uintptr_t)a.residual & 7) == 0)) &&
-                  (!(a.epi & MTS_EPI_BIAS) || ((uintptr_t)a.bias & 15) == 0);
+  const bool ok = g224_simple_epi_ok(a, 8) && g224_c_bf16_ok(a) && (a.M % 256 == 0) && (a.N % G224_BN == 0) && (a.K % (2 * BK) == 0) && a.K >= 4 * BK &&
+                  a.ksplit == a.K && g224_operand_ok(a.A, a.lda, g224_kmajor_span(256, a.lda, a.K)) &&
+                  g224_operand_ok(a.B, a.ldb, g224_kmajor_span(224, a.ldb, a.K));
   if (!ok) return -1;
   auto k = gemm_bf16_224p_kernel;
   if (int rc = mts_dyn_lds(k, P_LDS, "gemm224p")) return rc;
-  const int nt = (a.M / 256) * (a.N / P_BN);
+  const int nt = (a.M / 256) * (a.N / G224_BN);
   static std::atomic<int> ncu{0};
   if (!ncu) {
     int dev = 0, n = 0;

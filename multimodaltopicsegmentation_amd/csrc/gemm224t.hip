@@ -27,22 +27,16 @@
 // GemmArgs::chain set, the LAST-ARRIVING slice of each tile (below).
 #include <algorithm>
 #include <type_traits>
-#include "gemm_common.h"
+#include "gemm224_common.h"
 
 #define T_SLOT 32768
 #define T_LDS (4 * T_SLOT)
-#define T_BN 224
-#define T_HN 112
-
-typedef __attribute__((address_space(3))) void t_dlptr;
-
-struct TFrag { s16x4 lo, hi; };
 
 // (free function templates, not generic lambdas: clang rejects inline-asm operands that name variables captured by a generic lambda)
 // read operation K (0..29) of the unit whose A / B half images start at sbA / sbB into fragment set PS: 2 j, 2 j + 1 = the halves of B fragment j;
 // 14 + 2 i, 15 + 2 i = those of A fragment i
 template <int PS, int K>
-__device__ __forceinline__ void t_rd(TFrag (&fa)[2][8], TFrag (&fb)[2][7], const unsigned (&ax)[8], unsigned sbA, unsigned sbB) {
+__device__ __forceinline__ void t_rd(frag_raw (&fa)[2][8], frag_raw (&fb)[2][7], const unsigned (&ax)[8], unsigned sbA, unsigned sbB) {
   constexpr int req = K >> 1, hi = K & 1;
   if constexpr (req < 7) {
     const unsigned ad = ax[req] + sbB;
@@ -58,18 +52,14 @@ __device__ __forceinline__ void t_rd(TFrag (&fa)[2][8], TFrag (&fb)[2][7], const
 // (blocks 0..5: operations 5 I .. 5 I + 4, behind a wait that keeps at most 15 LDS operations of the wave in flight), behind the sixth the
 // block's copy
 template <int PS, int I, bool NXT, class Copy>
-__device__ __forceinline__ void t_block(f32x4 (&acc)[8][7], TFrag (&fa)[2][8], TFrag (&fb)[2][7], bf16x8 (&ob)[7], const unsigned (&ax)[8],
+__device__ __forceinline__ void t_block(f32x4 (&acc)[8][7], frag_raw (&fa)[2][8], frag_raw (&fb)[2][7], bf16x8 (&ob)[7], const unsigned (&ax)[8],
                                         unsigned sbA, unsigned sbB, Copy&& cp) {
   if constexpr (NXT && I < 6) lgkm_wait<10>();
   if constexpr (I == 0) {
 #pragma unroll
-    for (int j = 0; j < 7; ++j) {
-      asm volatile("" : "+v"(fb[PS][j].lo), "+v"(fb[PS][j].hi));
-      ob[j] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(fb[PS][j].lo, fb[PS][j].hi, 0, 1, 2, 3, 4, 5, 6, 7));
-    }
+    for (int j = 0; j < 7; ++j) ob[j] = frag_finish(fb[PS][j]);
   }
-  asm volatile("" : "+v"(fa[PS][I].lo), "+v"(fa[PS][I].hi));
-  const bf16x8 va = __builtin_bit_cast(bf16x8, __builtin_shufflevector(fa[PS][I].lo, fa[PS][I].hi, 0, 1, 2, 3, 4, 5, 6, 7));
+  const bf16x8 va = frag_finish(fa[PS][I]);
 #define T_SB __builtin_amdgcn_sched_barrier(0)
 #define T_MF(j_) T_SB; acc[I][j_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ob[j_], va, acc[I][j_], 0, 0, 0); T_SB;
 #define T_RD(k_) if constexpr (NXT && I < 6) t_rd<PS ^ 1, (I < 6 ? 5 * I + (k_) : 0)>(fa, fb, ax, sbA, sbB);
@@ -92,8 +82,8 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_224t_kernel(const GemmArgs a
   const int lane = tid & 63;
   const int wave_u = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave_u >> 1, wn = wave_u & 1;
-  const int r16 = lane & 15, g = lane >> 4, q = r16 >> 2, p = r16 & 3;
-  const int ntn = a.N / T_BN, ntm = a.M / 256, nt = ntn * ntm, ntot = nt * splits;
+  const int r16 = lane & 15, g = lane >> 4;
+  const int ntn = a.N / G224_BN, ntm = a.M / 256, nt = ntn * ntm, ntot = nt * splits;
   // ---- workgroup -> (slice, tile).  Workgroups b, b + 8, .. run on one XCD (own L2): an XCD gets a contiguous run of ids; ids walk one
   // slice after the other, inside a slice bands of four tile rows, column-major inside a band -- the 32 workgroups an XCD runs at a time
   // share 4 A panels and up to 8 B panels of ONE k range.
@@ -105,10 +95,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_224t_kernel(const GemmArgs a
     if (second) id -= ntot;
     z = id / nt;
     const int tl = id - z * nt;
-    const int band = tl / (4 * ntn), within = tl - band * 4 * ntn;
-    const int rows = min(4, ntm - band * 4);
-    bm0 = (band * 4 + within % rows) * 256;
-    bn0 = (within / rows) * T_BN;
+    tile_origin(tl, ntn, ntm, 1, bm0, bn0);
   }
   const int kbeg = z * a.ksplit;
   const int kend = min(a.K, kbeg + a.ksplit);
@@ -116,43 +103,33 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_224t_kernel(const GemmArgs a
   const bf16_t* __restrict__ A = reinterpret_cast<const bf16_t*>(second ? A2 : a.A);
   const bf16_t* __restrict__ B = reinterpret_cast<const bf16_t*>(second ? B2 : a.B);
 
-  // ---- copies.  A piece = 4 k-rows x 256 B of one half image, lane-contiguous in the LDS (16 B per lane): lane (lr = lane >> 4, c16 = lane & 15)
-  // fills k-row lr, 32-B slot c16 >> 1, half c16 & 1; slot s of k-row r holds source column block s ^ key(r), key(r) = (r & 3) | (((r >> 3) & 1) << 2)
-  // (gemm_common.h strided_off) -- r = 4 piece + lr, so the key is lr | (bit 1 of the piece number << 2): two lane offsets per operand.
-  // B half images hold 112 used columns of 128: the lanes of the unused 16 fetch 16 columns further left (nobody reads what they bring, and
-  // the last tile column never reaches past the matrix).
-  const int lr = lane >> 4, c16 = lane & 15;
+  // ---- copies.  A piece = 4 k-rows x 256 B of one half image, lane-contiguous in the LDS (16 B per lane); two lane offsets per operand, by bit 1
+  // of the piece number (strided_copy_offsets, gemm224_common.h).  B half images hold 112 used columns of 128: their offsets are clipped (the
+  // lanes of the unused 16 fetch 16 columns further left: nobody reads what they bring, and the last tile column never reaches past the matrix).
   unsigned voA[2], voB[2];
-#pragma unroll
-  for (int par = 0; par < 2; ++par) {
-    const int key = lr | (par << 2);
-    const int col = (((c16 >> 1) ^ key) << 4) + ((c16 & 1) << 3);
-    voA[par] = (unsigned)(lr * a.lda + col) * 2u;
-    voB[par] = (unsigned)(lr * a.ldb + (col >= T_HN ? col - 16 : col)) * 2u;
-  }
-  const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)(A + (size_t)kbeg * a.lda + bm0), 0, 0x7ffffff0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void*)(B + (size_t)kbeg * a.ldb + bn0), 0, 0x7ffffff0, 0x00020000);
+  strided_copy_offsets(lane, a.lda, 0, voA);
+  strided_copy_offsets(lane, a.ldb, G224_HN, voB);
+  const __amdgpu_buffer_rsrc_t rsA = make_rsrc(A + (size_t)kbeg * a.lda + bm0);
+  const __amdgpu_buffer_rsrc_t rsB = make_rsrc(B + (size_t)kbeg * a.ldb + bn0);
   // wave w copies pieces 4 (w & 1) .. + 3 of half image w >> 1, of A (copies 0..3) and of B (copies 4..7)
   const int h_w = wave_u >> 1, pi0 = (wave_u & 1) * 4;
-  const int sA0 = (4 * pi0 * a.lda + h_w * 128) * 2, sB0 = (4 * pi0 * a.ldb + h_w * T_HN) * 2;
+  const int sA0 = (4 * pi0 * a.lda + h_w * 128) * 2, sB0 = (4 * pi0 * a.ldb + h_w * G224_HN) * 2;
   const int rowA4 = 8 * a.lda, rowB4 = 8 * a.ldb;                 // bytes per 4 k-rows
   const int unitA = 64 * a.lda, unitB = 64 * a.ldb;               // bytes per unit
   char* const dst_w = smem + h_w * 8192 + pi0 * 1024;
   auto copy1 = [&](auto C, int u) {
     constexpr int c = decltype(C)::value;
     char* d = dst_w + (u & 3) * T_SLOT + (c & 3) * 1024;
-    if constexpr (c < 4) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (t_dlptr*)d, 16, voA[(c >> 1) & 1], sA0 + c * rowA4 + u * unitA, 0, 0);
-    else __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (t_dlptr*)(d + 16384), 16, voB[(c >> 1) & 1], sB0 + (c - 4) * rowB4 + u * unitB, 0, 0);
+    if constexpr (c < 4) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (dlptr_t*)d, 16, voA[(c >> 1) & 1], sA0 + c * rowA4 + u * unitA, 0, 0);
+    else __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (dlptr_t*)(d + 16384), 16, voB[(c >> 1) & 1], sB0 + (c - 4) * rowB4 + u * unitB, 0, 0);
   };
   // ---- fragment reads: X[k = 8 g + q (+ 4), column block c, columns 4 p ..] through two transposing reads (gemm_common.h frag_strided)
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-  const unsigned sx = (unsigned)((8 * g + q) * 256 + 8 * p + ((q | ((g & 1) << 2)) << 5));
   unsigned ax[8];
-#pragma unroll
-  for (int c = 0; c < 8; ++c) ax[c] = lds0 + (sx ^ (unsigned)(c << 5));
+  strided_frag_offsets(r16, g, lds0, ax);
   const unsigned offA = wm * 8192, offB = 16384 + wn * 8192;
 
-  TFrag fa[2][8], fb[2][7];
+  frag_raw fa[2][8], fb[2][7];
   f32x4 acc[8][7];
 #pragma unroll
   for (int i = 0; i < 8; ++i)
@@ -209,7 +186,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_224t_kernel(const GemmArgs a
   }
 
   // ---- epilogue: fp32 tile -> C, or -> this slice's plane of the slab ------------------------------------------------------------------
-  const int m0 = bm0 + wm * 128, n0 = bn0 + wn * T_HN;
+  const int m0 = bm0 + wm * 128, n0 = bn0 + wn * G224_HN;
   float* __restrict__ Cb = a.slab ? (second ? slab2 : a.slab) + (size_t)z * a.M * a.N : reinterpret_cast<float*>(a.C);
   const size_t ldo = a.slab ? (size_t)a.N : (size_t)a.ldc;
   const bool accum = !a.slab && (a.epi & MTS_EPI_ACCUM);
@@ -233,7 +210,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_224t_kernel(const GemmArgs a
   // (the XCDs' L2s are not coherent with each other; /opt/skills guide, "In-launch split-K reduction"); a.chain[tile] was zeroed by the launcher.
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  const int tile = (bm0 / 256) * ntn + bn0 / T_BN;
+  const int tile = (bm0 / 256) * ntn + bn0 / G224_BN;
   if (tid == 0) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -272,10 +249,9 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_224t_kernel(const GemmArgs a
 bool mts_gemm224t_applies(const GemmArgs& a, int layout, bool c_is_f32, int splits) {
   if (!c_is_f32 || layout != MTS_TN) return false;
   const int last = a.K - (splits - 1) * a.ksplit;           // k range of the last slice
-  const size_t spanA = ((size_t)a.ksplit + 64) * a.lda * 2, spanB = ((size_t)a.ksplit + 64) * a.ldb * 2;   // byte offsets inside a slice stay below 2^31
-  return (a.epi & ~MTS_EPI_ACCUM) == 0 && (a.M % 256 == 0) && (a.N % T_BN == 0) && (a.K % 64 == 0) && (a.ksplit % 64 == 0) &&
-         a.ksplit >= 128 && last >= 128 && (a.lda % 8 == 0) && (a.ldb % 8 == 0) && (((uintptr_t)a.A & 15) == 0) && (((uintptr_t)a.B & 15) == 0) &&
-         (a.ldc % 4 == 0) && (((uintptr_t)a.C & 15) == 0) && spanA < 0x7ff00000u && spanB < 0x7ff00000u && (splits == 1 || a.slab);
+  return (a.epi & ~MTS_EPI_ACCUM) == 0 && (a.M % 256 == 0) && (a.N % G224_BN == 0) && (a.K % 64 == 0) && (a.ksplit % 64 == 0) &&
+         a.ksplit >= 128 && last >= 128 && g224_operand_ok(a.A, a.lda, g224_strided_span(a.ksplit, a.lda)) &&
+         g224_operand_ok(a.B, a.ldb, g224_strided_span(a.ksplit, a.ldb)) && (a.ldc % 4 == 0) && (((uintptr_t)a.C & 15) == 0) && (splits == 1 || a.slab);
 }
 
 // called from mts_launch_gemm224 (gemm224.hip); -1: shape not covered here
@@ -283,7 +259,7 @@ int mts_launch_gemm224t(const GemmArgs& a, int layout, bool c_is_f32, int splits
   if (!mts_gemm224t_applies(a, layout, c_is_f32, splits)) return -1;
   auto k = gemm_bf16_224t_kernel<false>;
   if (int rc = mts_dyn_lds(k, T_LDS, "gemm224t")) return rc;
-  const int nt = (a.M / 256) * (a.N / T_BN);
+  const int nt = (a.M / 256) * (a.N / G224_BN);
   if (a.chain) {                                       // the arrival tickets of the in-launch combine: zeroed on the stream, every call
     hipError_t e = hipMemsetAsync(a.chain, 0, ((size_t)nt * sizeof(unsigned) + 15) & ~(size_t)15, st);
     if (e != hipSuccess) { mts_set_error("gemm224t: hipMemsetAsync: %s", hipGetErrorString(e)); return MTS_ERR_LAUNCH; }
@@ -297,7 +273,7 @@ int mts_launch_gemm224t_pair(const GemmArgs& a, int splits, const void* A2, cons
   if (!mts_gemm224t_applies(a, MTS_TN, true, splits) || !a.slab || a.chain || !A2 || !B2 || !slab2 || (((uintptr_t)A2 | (uintptr_t)B2) & 15)) return -1;
   auto k = gemm_bf16_224t_kernel<true>;
   if (int rc = mts_dyn_lds(k, T_LDS, "gemm224t")) return rc;
-  const int nt = (a.M / 256) * (a.N / T_BN);
+  const int nt = (a.M / 256) * (a.N / G224_BN);
   hipLaunchKernelGGL(k, dim3(2 * nt * splits), dim3(256), T_LDS, st, a, splits, A2, B2, slab2);
   return MTS_OK;
 }

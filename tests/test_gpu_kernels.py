@@ -154,6 +154,41 @@ def test_gemm_224_barrier_schedules_agree_bitwise(ops, layout, M, N, K):
     _close(outs[0][1], ref, 1e-4, 1e-4 * math.sqrt(K), f'{layout} mid-tile barrier fp32 C')
 
 
+def test_gemm_224p_walks_several_tiles_per_workgroup(ops):
+    """The persistent forward kernel (gemm224p.hip) with MORE tiles than CUs: 2 * cus + 4 tiles, so every workgroup walks two tiles and a few walk
+    three -- the tile-to-tile path (the next tile's resources, the counted wait at the round boundary, the bias row copied behind the barrier) that
+    the other shapes of this file, at most one tile per workgroup, never reach.  Default dispatch with bias + column scale (the scaled columns end
+    inside the second tile column) and gemm_variant 12 with bias + residual: bf16 C bitwise that of the eight-wave kernel (6) and of the
+    one-tile-per-workgroup kernel (9); both calls must have run on the 224-wide persistent plan."""
+    from multimodaltopicsegmentation_amd import _lib as L
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    M, N, K = 256 * (cus + 2), 448, 256
+    g = torch.Generator(device=DEV).manual_seed(65)
+    a = torch.randn(M, K, generator=g, device=DEV).to(torch.bfloat16)
+    b = torch.randn(N, K, generator=g, device=DEV).to(torch.bfloat16)
+    bias = torch.randn(N, generator=g, device=DEV)
+    res = torch.randn(M, N, generator=g, device=DEV).to(torch.bfloat16)
+    plan = ctypes_int()
+    try:
+        L.check(L.lib.mts_set_option(b'gemm_tile', 224))
+        for variant, kw in ((0, dict(colscale=0.125, ncols_scaled=224 + 100)), (12, dict(residual=res))):
+            outs = {}
+            for v in (variant, 6, 9):
+                L.check(L.lib.mts_set_option(b'gemm_variant', v))
+                o = torch.full((M, N), float('nan'), dtype=torch.bfloat16, device=DEV)
+                ops.gemm(L.NT, a, b, o, M=M, N=N, K=K, bias=bias, **kw)
+                if v == variant:
+                    L.lib.mts_gemm_last_plan(plan.ref, None)
+                    assert plan.value == 224, (variant, plan.value)
+                outs[v] = o
+            assert not torch.isnan(outs[variant].float()).any(), variant
+            assert torch.equal(outs[variant].view(torch.int16), outs[6].view(torch.int16)), (variant, 6)
+            assert torch.equal(outs[variant].view(torch.int16), outs[9].view(torch.int16)), (variant, 9)
+    finally:
+        L.check(L.lib.mts_set_option(b'gemm_variant', 0))
+        L.check(L.lib.mts_set_option(b'gemm_tile', 0))
+
+
 @pytest.mark.parametrize('M,N,K,splits', [(256, 224, 128, 1), (256, 224, 192, 1), (512, 448, 256, 1), (768, 224, 1088, 1), (512, 448, 2304, 3), (256, 1792, 2048, 16),
                                           (1792, 1792, 4096, 4), (5376, 1792, 2048, 0), (2048, 1792, 16384, 0)])
 def test_gemm_224t_matches_the_eight_wave_kernel_bitwise(ops, M, N, K, splits):
