@@ -301,6 +301,66 @@ int mts_frame_edges(void* stream, int in_dtype, int out_dtype, int n_sent, int D
                     const uint8_t* doc_last,    /* device [n_sent]: 1 on the last sentence of a document */
                     void* out,                  /* device: row s at out + s * ld_out, D columns written */
                     int64_t ld_out);
+/* MFCC SENTENCE FEATURES FROM RESIDENT WAVEFORMS (audio.ResidentAudio.mfcc; reference: extract_acoustic_features.py:58-72, the `mfcc`
+ * encoder of train_fit.py:245-248: per sentence librosa.feature.mfcc(y, sr, n_mfcc=50) and its librosa.feature.delta, then mean and std over
+ * the frames of both -- the last step is mts_frame_pool with MTS_POOL_MEAN and with_std on the [mfcc | delta] frames), csrc/mfcc.hip.
+ * The definition is librosa 0.8.1's at the reference's arguments, restated; parity with librosa itself is UNPINNED (the tests' oracle is a
+ * NumPy restatement of these lines).  Sentence s is the n = sent_len[s] samples of `wave` from sent_start[s] (both clamped into the
+ * buffer before an address is formed; offsets are 64-bit) and owns the T = frame_start[s + 1] - frame_start[s] rows of the outputs from
+ * row frame_start[s] (entries clamped into 0 .. total_frames); the caller sets T = 1 + n / hop (librosa's center=True).
+ *   frame t   the n_fft samples t * hop - n_fft / 2 .. t * hop + n_fft / 2 - 1 of the sentence; an index outside 0 .. n - 1 is reflected about
+ *             the sentence's OWN ends without repeating the end sample (np.pad(y, n_fft / 2, 'reflect'): the fold of period 2 (n - 1), n == 1
+ *             constant), so every n >= 1 is defined and the neighbouring audio is never read;
+ *   window    x[i] = fl(y[.] * window[i]); the host passes the periodic Hann window 0.5 - 0.5 cos(2 pi i / n_fft);
+ *   power     P[k] = |X[k]|^2, k = 0 .. n_fft / 2, X = rfft(x) computed as an N = n_fft / 2 point complex transform of z[i] = x[2 i] + i x[2 i + 1]:
+ *             Stockham passes Ns = 1, 4, 16, .. of radix 4 -- v_r = in[j + r N / 4] * tw[r k n_fft / (4 Ns)] (k = j mod Ns; no product in the first
+ *             pass), a0 = v0 + v2, a1 = v0 - v2, a2 = v1 + v3, a3 = -i (v1 - v3), out[4 (j - k) + k + {0, Ns, 2 Ns, 3 Ns}] = a0 + a2, a1 + a3,
+ *             a0 - a2, a1 - a3 -- and one radix-2 pass (a + w b, a - w b) last when log2 N is odd; then X[k] = E + tw[k] O with
+ *             E = (Z[k] + conj Z[N - k]) / 2, O = -i (Z[k] - conj Z[N - k]) / 2, Z[N] = Z[0];  P = fl(fl(Xr^2) + fl(Xi^2)).  A complex product is
+ *             four fp32 products and two sums, each rounded (no contraction).  tw[m] = exp(-2 pi i m / n_fft), m < n_fft, as (cos, -sin) pairs:
+ *             window, tw, the mel weights and the DCT table are built by the host in fp64 and rounded ONCE to fp32; no sine, cosine or fast
+ *             intrinsic is evaluated on the device;
+ *   mel       M[m] = sum_j mel_w[mel_ptr[m] + j] * P[mel_first[m] + j], j = 0 .. mel_ptr[m + 1] - mel_ptr[m] - 1: ONE chain from 0 in ascending j,
+ *             product and sum each rounded; filter-major, no scatter (table entries are clamped into the tables and the spectrum);
+ *   dB        d = fl(10 * log10f(max(1e-10, M))), then max(d, fl(top - 80)), top = the same dB of the LARGEST mel power over all frames and bands
+ *             of the sentence (the maximum is exact);
+ *   MFCC      c[i] = sum_m d[m] dct[i][m]: eight fma chains (chain u takes m = u, u + 8, ..., ascending) added as ((a0 + a1) + (a2 + a3)) +
+ *             ((a4 + a5) + (a6 + a7));
+ *   delta     scipy.signal.savgol_filter(c, 9, polyorder=1, deriv=1, mode='interp') over the frames of the sentence: for 4 <= t <= T - 5,
+ *             D[t] = fl(S / 60), S = sum_{k=1..4} fl(k * fl(c[t + k] - c[t - k])) from 0 in ascending k; D[0..3] = D[4] and D[T-4..T-1] = D[T-5]
+ *             (the same bits); T < 9 (librosa raises there) is defined as D = 0.  The delta reads the fp32 MFCC, never a rounded output.
+ * All run on the caller's stream, use no atomics and no dependence between workgroups of one launch, write every output element exactly
+ * once and give the same bits for the same inputs.  MTS_ERR_INVALID before any device work: a null pointer, an unknown out_dtype, a size
+ * < 1, n_fft no power of two in 64 .. 4096, n_mfcc > n_mels, ld_out < 2 n_mfcc, a workspace smaller than mts_mfcc_frames_workspace.
+ * MTS_ERR_UNSUPPORTED: a DCT table beyond a workgroup's 64 KiB of LDS, more frames than one launch covers.
+ *   mts_mel_frames   wave -> mel [total_frames, n_mels] fp32, the mel POWER before the log; one workgroup per frame.  A sentence without
+ *                    samples writes 0.
+ *   mts_mfcc_frames  mel -> out: row f at out + f * ld_out in out_dtype MTS_F32 | MTS_BF16 (bf16: ONE rounding of the fp32 value), columns
+ *                    [0, n_mfcc) the MFCC, [n_mfcc, 2 n_mfcc) the delta; ld_out may exceed 2 n_mfcc and nothing outside the block is touched.
+ *                    Three launches: the sentences' tops, the DCT into the workspace's fp32 MFCC, the block with the delta. */
+int mts_mel_frames(void* stream, int n_sent, int n_fft, int hop, int n_mels,
+                   const float* wave,           /* device [total_samples] */
+                   int64_t total_samples,
+                   const int64_t* sent_start,   /* device [n_sent]: first sample of the sentence */
+                   const int64_t* sent_len,     /* device [n_sent]: its samples */
+                   const int64_t* frame_start,  /* device [n_sent + 1], ascending */
+                   int64_t total_frames,
+                   const float* window,         /* device [n_fft] */
+                   const float* twiddle,        /* device [n_fft, 2] */
+                   const int32_t* mel_first,    /* device [n_mels]: first FFT bin of the filter */
+                   const int32_t* mel_ptr,      /* device [n_mels + 1]: its weights are mel_w[mel_ptr[m] .. mel_ptr[m + 1]) */
+                   const float* mel_w,          /* device [mel_nnz] */
+                   int mel_nnz,
+                   float* mel);                 /* device [total_frames, n_mels] out */
+size_t mts_mfcc_frames_workspace(int n_sent, int64_t total_frames, int n_mfcc);
+int mts_mfcc_frames(void* stream, int out_dtype, int n_sent, int n_mels, int n_mfcc,
+                    const float* mel,           /* device [total_frames, n_mels] */
+                    int64_t total_frames,
+                    const int64_t* frame_start, /* device [n_sent + 1], ascending */
+                    const float* dct,           /* device [n_mfcc, n_mels] */
+                    void* workspace, size_t workspace_bytes,
+                    void* out,                  /* device: row f at out + f * ld_out, 2 n_mfcc columns written */
+                    int64_t ld_out);
 
 /* ---------------------------------------------------------------------------------------------
  * LayerNorm family (biased variance, eps inside sqrt).

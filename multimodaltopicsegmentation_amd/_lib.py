@@ -140,6 +140,9 @@ SIGNATURES = {
     'mts_pca_project': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'mts_frame_pool': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, C.c_int64, _vp, _vp, C.c_int64]),
     'mts_frame_edges': (_i, [_vp, _i, _i, _i, _i, _i, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64]),
+    'mts_mel_frames': (_i, [_vp, _i, _i, _i, _i, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    'mts_mfcc_frames_workspace': (_sz, [_i, C.c_int64, _i]),
+    'mts_mfcc_frames': (_i, [_vp, _i, _i, _i, _i, _vp, C.c_int64, _vp, _vp, _vp, _sz, _vp, C.c_int64]),
 }
 
 _missing = []

@@ -1,0 +1,277 @@
+"""MFCC sentence features from resident waveforms.
+
+Every audio encoder the reference trains on is a pretrained network (x-vectors, openl3, CREPE, wav2vec, ECAPA) -- but one: ``mfcc``
+(train_fit.py:245-248, ``'mfcc': 200``).  extract_acoustic_features.py:58-72 defines it: per sentence ``librosa.feature.mfcc(y, sr,
+n_mfcc=50)``, its ``librosa.feature.delta``, then ``np.nanmean`` and ``np.nanstd`` over the frames of both: a 200-wide sentence vector from
+nothing but the waveform and the sentence times.  Here the waveforms are uploaded ONCE and the frames are made in HBM by csrc/mfcc.hip:
+
+  * ``ResidentAudio(waves, spans, device)`` holds the concatenated fp32 waveform and the sentence table on the device;
+  * ``audio.mfcc()`` is a ``frames.ResidentFrames`` of [mfcc(50) | delta(50)] frames (``ops.mel_frames``: framing, window, FFT, mel;
+    ``ops.mfcc_frames``: dB, DCT, delta);
+  * ``audio.mfcc().pool('mean_std')`` -- ``audio.mfcc_stats()`` -- is, column for column, the reference's [mean x, mean dx, std x, std dx],
+    and ``ResidentCorpus.with_frames(audio.mfcc(), 'mean_std', field=...)`` carries it into a corpus.
+
+The definition is librosa 0.8.1's (the reference's requirements.txt) at the arguments the reference passes, restated: sr = 16000; frames of
+n_fft = 2048 every hop = 512 samples, centred, the sentence reflect-padded about its OWN ends (T = 1 + n // hop frames); periodic Hann
+window; power spectrum; 128 Slaney mel filters from 0 to sr / 2 with area normalisation; 10 log10(max(1e-10, .)) clamped 80 dB below the
+sentence's largest value; orthonormal DCT-II, coefficients 0 .. 49; delta = scipy.signal.savgol_filter(x, 9, polyorder=1, deriv=1,
+mode='interp') along the frames.  The arithmetic is stated in include/mts.h.
+
+Deviations, on purpose.  Parity with librosa itself is UNPINNED: librosa cannot run where this was built, so the tests check against a NumPy
+restatement of the lines above.  A non-finite sample is refused at upload (np.nanmean would skip what it made of it).  The sums run in the
+kernels' fixed order.  A sentence shorter than 8 * hop = 4096 samples (0.256 s) is refused here where upstream raises (librosa's delta
+needs 9 frames).  The reference's prosodic encoder (``pyin`` pitch, pauses; ``prosodic: 167``) is not built.
+"""
+import os
+
+import numpy as np
+import torch
+
+from .frames import ResidentFrames
+
+_CHECK_SAMPLES = 1 << 22                   # samples per slice of the upload's finiteness check
+_DELTA_FRAMES = 9                          # librosa.feature.delta's default width: it raises for fewer frames
+_TABLES = {}                               # (sr, n_fft, n_mels, n_mfcc) -> the host tables
+
+
+def _hz_to_mel(f):
+    """Slaney's scale (librosa's htk=False): 200 / 3 Hz per mel below 1 kHz, ln(6.4) / 27 per mel in log-frequency above"""
+    f = np.asarray(f, dtype=np.float64)
+    lin = f * 3.0 / 200.0
+    log = 15.0 + np.log(np.maximum(f, 1e-300) / 1000.0) * (27.0 / np.log(6.4))
+    return np.where(f >= 1000.0, log, lin)
+
+
+def _mel_to_hz(m):
+    m = np.asarray(m, dtype=np.float64)
+    return np.where(m >= 15.0, 1000.0 * np.exp((m - 15.0) * (np.log(6.4) / 27.0)), m * 200.0 / 3.0)
+
+
+def mel_filterbank(sr, n_fft, n_mels):
+    """-> fp64 [n_mels, 1 + n_fft // 2]: triangular filters on n_mels + 2 points equally spaced in mel between 0 and sr / 2, evaluated at
+    the bin frequencies np.linspace(0, sr / 2, 1 + n_fft // 2), filter m scaled by 2 / (f[m + 2] - f[m]) (Slaney's area normalisation)"""
+    bins = np.linspace(0.0, sr / 2.0, 1 + n_fft // 2)
+    edges = _mel_to_hz(np.linspace(_hz_to_mel(0.0), _hz_to_mel(sr / 2.0), n_mels + 2))
+    width = np.diff(edges)
+    ramps = edges[:, None] - bins[None, :]
+    rising = -ramps[:-2] / width[:-1, None]
+    falling = ramps[2:] / width[1:, None]
+    return np.maximum(0.0, np.minimum(rising, falling)) * (2.0 / (edges[2:] - edges[:-2]))[:, None]
+
+
+def pack_filterbank(fb):
+    """the filters as the kernel reads them: (first, ptr, weights) -- filter m owns the bins first[m] .. first[m] + ptr[m + 1] - ptr[m] - 1
+    with the fp32 weights[ptr[m] : ptr[m + 1]] (its run from the first to the last non-zero bin)"""
+    first, ptr, weights = [], [0], []
+    for row in np.asarray(fb, dtype=np.float32):
+        nz = np.flatnonzero(row)
+        if nz.size == 0:
+            raise ValueError('a mel filter is empty: too many bands for this n_fft')
+        first.append(int(nz[0]))
+        weights.append(row[nz[0]:nz[-1] + 1])
+        ptr.append(ptr[-1] + int(nz[-1] - nz[0] + 1))
+    return np.asarray(first, dtype=np.int32), np.asarray(ptr, dtype=np.int32), np.concatenate(weights).astype(np.float32)
+
+
+def mfcc_tables(sr=16000, n_fft=2048, n_mels=128, n_mfcc=50):
+    """-> dict of the host tables, built in fp64 and rounded once to fp32 (cached per parameter set): ``window`` [n_fft] periodic Hann;
+    ``twiddle`` [n_fft, 2] (cos, -sin)(2 pi m / n_fft); ``mel_first`` / ``mel_ptr`` / ``mel_w`` the packed mel filters; ``dct``
+    [n_mfcc, n_mels] the orthonormal DCT-II"""
+    key = (int(sr), int(n_fft), int(n_mels), int(n_mfcc))
+    if key in _TABLES:
+        return _TABLES[key]
+    sr, n_fft, n_mels, n_mfcc = key
+    if n_fft < 64 or n_fft > 4096 or n_fft & (n_fft - 1):
+        raise ValueError(f'n_fft must be a power of two in 64 .. 4096, not {n_fft}')
+    if not 1 <= n_mfcc <= n_mels:
+        raise ValueError(f'n_mfcc must be in 1 .. n_mels = {n_mels}, not {n_mfcc}')
+    phase = 2.0 * np.pi * np.arange(n_fft, dtype=np.float64) / n_fft
+    first, ptr, w = pack_filterbank(mel_filterbank(sr, n_fft, n_mels))
+    m = np.arange(n_mels, dtype=np.float64)
+    dct = np.sqrt(2.0 / n_mels) * np.cos(np.pi * np.arange(n_mfcc, dtype=np.float64)[:, None] * (2.0 * m[None, :] + 1.0) / (2.0 * n_mels))
+    dct[0] *= np.sqrt(0.5)
+    _TABLES[key] = {'window': (0.5 - 0.5 * np.cos(phase)).astype(np.float32),
+                    'twiddle': np.stack([np.cos(phase), -np.sin(phase)], axis=1).astype(np.float32),
+                    'mel_first': first, 'mel_ptr': ptr, 'mel_w': w, 'dct': dct.astype(np.float32)}
+    return _TABLES[key]
+
+
+def uniform_spans(n_samples, interval=1.0, sr=16000):
+    """-> the (start, end) sample spans of the reference's uniform units (extract_embeddings_inference.py:243-247, :406-408), for
+    ``ResidentAudio(..., unit='samples')``: ``int((n_samples / sr) // interval)`` units, unit i = [int(sr * interval * i),
+    int(sr * (interval * i + 1))).  The window is ONE second whatever the interval: that is what upstream computes."""
+    n = int((n_samples / sr) // interval)
+    return [(int(sr * (interval * i)), int(sr * (interval * i + 1))) for i in range(n)]
+
+
+def load_wav(directory, files):
+    """-> a list over documents of fp32 waveforms read from ``<directory>/<file>.wav``: 16 kHz mono PCM through scipy.io.wavfile; int16 is
+    scaled by 1 / 32768 (int32 by 2^-31, uint8 centred and scaled by 1 / 128, float as it is).  ValueError for another rate or channel
+    count: resampling and other containers are the caller's, who can pass arrays to ResidentAudio directly."""
+    from scipy.io import wavfile
+    out = []
+    for name in files:
+        path = os.path.join(directory, name if str(name).endswith('.wav') else f'{name}.wav')
+        rate, data = wavfile.read(path)
+        if rate != 16000:
+            raise ValueError(f'load_wav: {path} is sampled at {rate} Hz; 16000 is expected (resample before)')
+        if data.ndim != 1:
+            raise ValueError(f'load_wav: {path} has {data.shape[1]} channels; mono is expected')
+        if data.dtype == np.int16:
+            data = data.astype(np.float32) / 32768.0
+        elif data.dtype == np.int32:
+            data = (data.astype(np.float64) / 2147483648.0).astype(np.float32)
+        elif data.dtype == np.uint8:
+            data = (data.astype(np.float32) - 128.0) / 128.0
+        out.append(np.ascontiguousarray(data, dtype=np.float32))
+    return out
+
+
+class ResidentAudio:
+    """The waveforms of a corpus in HBM: ``wave`` fp32 [total_samples] (the documents one after another, ONE upload), ``sent_start`` /
+    ``sent_len`` (int64 [total_sentences]: sentence s is the samples sent_start[s] .. sent_start[s] + sent_len[s] of ``wave``).
+
+    ``waves``: a list over documents of 1-d float arrays at ``sr``.  ``spans``: a list over documents of (start, end) per sentence;
+    ``unit='seconds'`` converts as the reference does, ``int(sr * t)`` (extract_embeddings.py:108-109, :506-513), ``unit='samples'`` takes
+    integers; ``end`` is clipped to the document's length, as the slice ``audio[start:end]`` is.  Sentences may overlap or leave gaps.
+
+    Host tables: ``sentences`` (sentences per document), ``sample_counts`` (samples per sentence), ``frame_counts`` (frames per sentence
+    at the default hop of 512: 1 + n // 512), ``n_docs``, ``total_sentences``, ``total_samples``, ``total_frames``, ``nbytes``.  With a
+    CPU device only the host tables exist, as for ResidentFrames.
+
+    ValueError, naming the document and the sentence: an empty document, a wave that is not 1-d, a negative start, ``start >= end`` after
+    clipping, a sentence shorter than 8 * 512 = 4096 samples.  ValueError for a non-finite sample, found on the device at upload."""
+
+    DEFAULT_HOP = 512
+
+    def __init__(self, waves, spans, device, sr=16000, unit='seconds'):
+        if unit not in ('seconds', 'samples'):
+            raise ValueError("ResidentAudio: unit must be 'seconds' or 'samples'")
+        self.sr = int(sr)
+        self.device = torch.device(device)
+        if self.device.type == 'cuda' and self.device.index is None:
+            self.device = torch.device('cuda', torch.cuda.current_device())
+        if len(waves) == 0 or len(waves) != len(spans):
+            raise ValueError(f'ResidentAudio: {len(waves)} waveforms and {len(spans)} span lists; one list per document and at least one are expected')
+        parts, starts, lens, sentences, offset = [], [], [], [], 0
+        for d, (w, doc_spans) in enumerate(zip(waves, spans)):
+            a = w.detach().cpu().to(torch.float32).numpy() if isinstance(w, torch.Tensor) else np.asarray(w, dtype=np.float32)
+            if a.ndim != 1:
+                raise ValueError(f'ResidentAudio: the wave of document {d} is {a.ndim}-d; a 1-d array of samples is expected')
+            if a.shape[0] == 0:
+                raise ValueError(f'ResidentAudio: document {d} has no samples')
+            if len(doc_spans) == 0:
+                raise ValueError(f'ResidentAudio: document {d} has no sentences')
+            for s, (t0, t1) in enumerate(doc_spans):
+                b, e = (int(self.sr * t0), int(self.sr * t1)) if unit == 'seconds' else (int(t0), int(t1))
+                e = min(e, int(a.shape[0]))
+                if b < 0:
+                    raise ValueError(f'ResidentAudio: sentence {s} of document {d} starts at sample {b}')
+                if b >= e:
+                    raise ValueError(f'ResidentAudio: sentence {s} of document {d} is empty: samples {b} .. {e} of {int(a.shape[0])} (start >= end '
+                                     'after clipping to the document)')
+                self._refuse_short(e - b, self.DEFAULT_HOP, s, d)
+                starts.append(offset + b)
+                lens.append(e - b)
+            sentences.append(len(doc_spans))
+            parts.append(a)
+            offset += int(a.shape[0])
+        self.n_docs = len(sentences)
+        self.sentences = np.asarray(sentences, dtype=np.int64)
+        self.sample_counts = np.asarray(lens, dtype=np.int64)
+        self.frame_counts = 1 + self.sample_counts // self.DEFAULT_HOP
+        self.total_sentences = int(self.sentences.sum())
+        self.total_samples = offset
+        self.total_frames = int(self.frame_counts.sum())
+        self._start_host = np.asarray(starts, dtype=np.int64)
+        self._doc_offset = np.concatenate([[0], np.cumsum([p.shape[0] for p in parts])]).astype(np.int64)
+        self.wave = self.sent_start = self.sent_len = None
+        self._device_tables = {}
+        if self.device.type != 'cuda':
+            return
+        flat = torch.from_numpy(np.concatenate(parts)) if len(parts) > 1 else torch.from_numpy(np.ascontiguousarray(parts[0]))
+        del parts
+        self.wave = flat.to(self.device)
+        self.sent_start = torch.from_numpy(self._start_host).to(self.device)
+        self.sent_len = torch.from_numpy(self.sample_counts).to(self.device)
+        self._refuse_non_finite()
+
+    @staticmethod
+    def _refuse_short(n, hop, s, d):
+        if n < (_DELTA_FRAMES - 1) * hop:
+            raise ValueError(f'ResidentAudio: sentence {s} of document {d} has {n} samples, fewer than the {(_DELTA_FRAMES - 1) * hop} that give '
+                             f"{_DELTA_FRAMES} frames at a hop of {hop}: librosa's delta needs {_DELTA_FRAMES} frames and the reference raises there")
+
+    def _where(self, s):
+        """flat sentence index -> (document, sentence of the document)"""
+        ends = np.cumsum(self.sentences)
+        d = int(np.searchsorted(ends, s, side='right'))
+        return d, s - (int(ends[d - 1]) if d else 0)
+
+    def _refuse_non_finite(self):
+        """one pass over the resident waveform in slices (the check's temporary stays small); the first offender is named"""
+        for a in range(0, self.total_samples, _CHECK_SAMPLES):
+            ok = torch.isfinite(self.wave[a:a + _CHECK_SAMPLES])
+            if not bool(ok.all()):
+                i = a + int(torch.nonzero(~ok)[0])
+                d = int(np.searchsorted(self._doc_offset, i, side='right')) - 1
+                inside = np.flatnonzero((self._start_host <= i) & (i < self._start_host + self.sample_counts))
+                where = f' (in sentence {self._where(int(inside[0]))[1]})' if inside.size else ''
+                raise ValueError(f'ResidentAudio: sample {i - int(self._doc_offset[d])} of document {d}{where} is not finite (refused here: '
+                                 'np.nanmean would skip the frames it spoils)')
+
+    def __len__(self):
+        return self.n_docs
+
+    @property
+    def nbytes(self):
+        """bytes of the resident data (waveform, sentence table, the tables of the parameter sets used so far); 0 on a CPU device"""
+        held = [self.wave, self.sent_start, self.sent_len] + [t for tabs in self._device_tables.values() for t in tabs.values()]
+        return sum(t.numel() * t.element_size() for t in held if t is not None)
+
+    def _tables(self, n_mfcc, n_mels, n_fft):
+        key = (n_mfcc, n_mels, n_fft)
+        if key not in self._device_tables:
+            host = mfcc_tables(self.sr, n_fft, n_mels, n_mfcc)
+            self._device_tables[key] = {k: torch.from_numpy(v).to(self.device) for k, v in host.items()}
+        return self._device_tables[key]
+
+    def mfcc(self, n_mfcc=50, n_mels=128, n_fft=2048, hop=512, out_dtype=torch.float32):
+        """-> ``frames.ResidentFrames`` on the device: [total_frames, 2 n_mfcc] frames in ``out_dtype`` (torch.float32 | torch.bfloat16; bf16
+        is the fp32 value rounded once), columns [0, n_mfcc) the MFCC and [n_mfcc, 2 n_mfcc) its delta, with this audio's sentence table
+        (sentence s has 1 + n // hop frames).  Two entry points on the current stream (csrc/mfcc.hip); the mel matrix between them is freed
+        before returning.  ValueError: parameters the tables refuse, a sentence shorter than 8 * hop samples (named); RuntimeError on a CPU
+        device (there is no CPU fallback)."""
+        n_mfcc, n_mels, n_fft, hop = int(n_mfcc), int(n_mels), int(n_fft), int(hop)
+        if hop < 1:
+            raise ValueError(f'mfcc: hop must be positive, not {hop}')
+        if out_dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f'mfcc: out_dtype is torch.float32 or torch.bfloat16, not {out_dtype}')
+        host = mfcc_tables(self.sr, n_fft, n_mels, n_mfcc)
+        if hop != self.DEFAULT_HOP:
+            short = np.flatnonzero(self.sample_counts < (_DELTA_FRAMES - 1) * hop)
+            if short.size:
+                d, s = self._where(int(short[0]))
+                self._refuse_short(int(self.sample_counts[short[0]]), hop, s, d)
+        if self.device.type != 'cuda':
+            raise RuntimeError('ResidentAudio.mfcc runs on the GPU (there is no CPU fallback)')
+        del host
+        from . import ops
+        counts = 1 + self.sample_counts // hop
+        start = np.zeros(self.total_sentences + 1, dtype=np.int64)
+        np.cumsum(counts, out=start[1:])
+        total_frames = int(start[-1])
+        with torch.cuda.device(self.device):
+            tabs = self._tables(n_mfcc, n_mels, n_fft)
+            frame_start = torch.from_numpy(start).to(self.device)
+            mel = ops.mel_frames(self.wave, self.sent_start, self.sent_len, frame_start, total_frames, tabs['window'], tabs['twiddle'],
+                                 tabs['mel_first'], tabs['mel_ptr'], tabs['mel_w'], hop)
+            out = torch.empty((total_frames, 2 * n_mfcc), dtype=out_dtype, device=self.device)
+            ops.mfcc_frames(mel, frame_start, tabs['dct'], out)
+            del mel
+        return ResidentFrames.from_device(out, frame_start, self.sentences)
+
+    def mfcc_stats(self, **kw):
+        """-> [total_sentences, 4 n_mfcc] on the device: ``mfcc(**kw).pool('mean_std')``, the reference's ``mfcc`` sentence vector
+        [mean x, mean dx, std x, std dx] (200 wide at the defaults)"""
+        return self.mfcc(**kw).pool('mean_std')

@@ -109,6 +109,41 @@ class ResidentFrames:
         self.doc_last = torch.from_numpy(last).to(self.device)
         self._refuse_non_finite()
 
+    @classmethod
+    def from_device(cls, frames, frame_start, sentences):
+        """-> ResidentFrames that ADOPTS device tensors another stage made (``audio.ResidentAudio.mfcc``): ``frames`` a contiguous fp32 /
+        bf16 [total_frames, D] device matrix, ``frame_start`` the int64 [total_sentences + 1] table (device or host; ascending from 0 to
+        total_frames) and ``sentences`` the sentences per document.  Nothing is copied but the small table; the host tables and
+        ``doc_last`` are built from it and the finiteness check of the constructor runs.  ValueError: a matrix of another dtype, layout
+        or place, a table that does not fit it, a document without sentences, a sentence without frames."""
+        if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dim() == 2 and frames.is_contiguous()
+                and frames.dtype in _WIRE.values() and frames.shape[1] >= 1):
+            raise ValueError('ResidentFrames.from_device: frames must be a contiguous fp32 / bf16 [total_frames, D] device matrix')
+        sentences = np.asarray(sentences, dtype=np.int64).reshape(-1)
+        if sentences.size == 0 or (sentences < 1).any():
+            raise ValueError('ResidentFrames.from_device: every document needs at least one sentence')
+        start = (frame_start.detach().cpu().numpy() if isinstance(frame_start, torch.Tensor) else np.asarray(frame_start)).astype(np.int64)
+        if start.ndim != 1 or start.size != int(sentences.sum()) + 1 or start[0] != 0 or int(start[-1]) != int(frames.shape[0]):
+            raise ValueError(f'ResidentFrames.from_device: frame_start must run from 0 to {int(frames.shape[0])} over '
+                             f'{int(sentences.sum())} sentences')
+        counts = np.diff(start)
+        if (counts < 1).any():
+            raise ValueError(f'ResidentFrames.from_device: sentence {int(np.flatnonzero(counts < 1)[0])} of the table has no frames')
+        self = cls.__new__(cls)
+        self.wire, self.device, self.D = frames.dtype, frames.device, int(frames.shape[1])
+        self.n_docs, self.sentences, self.frame_counts = int(sentences.size), sentences, counts
+        self.total_sentences, self.total_frames = int(sentences.sum()), int(start[-1])
+        self._start_host = start
+        last = np.zeros(self.total_sentences, dtype=np.uint8)
+        last[np.cumsum(sentences) - 1] = 1
+        self._last_host = last
+        self.frames = frames
+        on_device = isinstance(frame_start, torch.Tensor) and frame_start.device == frames.device and frame_start.dtype == torch.int64
+        self.frame_start = frame_start.contiguous() if on_device else torch.from_numpy(start).to(frames.device)
+        self.doc_last = torch.from_numpy(last).to(frames.device)
+        self._refuse_non_finite()
+        return self
+
     def _refuse_non_finite(self):
         """one pass over the resident matrix in slices (the check's temporary stays small); the first offender is named"""
         for a in range(0, self.total_frames, _CHECK_ROWS):

@@ -349,6 +349,51 @@ def frame_edges(frames, frame_start, doc_last, out, mode='last'):
     return out
 
 
+def mel_frames(wave, sent_start, sent_len, frame_start, total_frames, window, twiddle, mel_first, mel_ptr, mel_w, hop, mel=None):
+    """the mel power spectrogram of every sentence of a resident waveform (include/mts.h mts_mel_frames): wave fp32 [total_samples];
+    sentence s is its sent_len[s] samples from sent_start[s] and owns the rows frame_start[s] .. frame_start[s + 1] of mel (all int64, on
+    the device).  window fp32 [n_fft], twiddle fp32 [n_fft, 2], the packed mel filters mel_first int32 [n_mels], mel_ptr int32
+    [n_mels + 1], mel_w fp32 [nnz].  -> mel fp32 [total_frames, n_mels], every element written."""
+    n_sent, n_fft, n_mels = sent_start.numel(), window.numel(), mel_first.numel()
+    assert wave.dim() == 1 and wave.dtype == torch.float32 and wave.is_contiguous() and wave.is_cuda
+    for t in (sent_start, sent_len, frame_start):
+        assert t.dtype == torch.int64 and t.dim() == 1 and t.is_contiguous() and t.device == wave.device
+    assert sent_len.numel() == n_sent and frame_start.numel() == n_sent + 1
+    for t in (window, twiddle, mel_w):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.device == wave.device
+    for t in (mel_first, mel_ptr):
+        assert t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous() and t.device == wave.device
+    assert twiddle.numel() == 2 * n_fft and mel_ptr.numel() == n_mels + 1
+    total_frames = int(total_frames)
+    if mel is None:
+        mel = torch.empty((max(total_frames, 0), n_mels), dtype=torch.float32, device=wave.device)
+    assert mel.dtype == torch.float32 and mel.is_contiguous() and mel.numel() == max(total_frames, 0) * n_mels and mel.device == wave.device
+    check(lib.mts_mel_frames(stream_ptr(), n_sent, n_fft, int(hop), n_mels, ptr(wave), wave.numel(), ptr(sent_start), ptr(sent_len),
+                             ptr(frame_start), total_frames, ptr(window), ptr(twiddle), ptr(mel_first), ptr(mel_ptr), ptr(mel_w), mel_w.numel(),
+                             ptr(mel)))
+    return mel
+
+
+def mfcc_frames(mel, frame_start, dct, out):
+    """MFCC and delta frames from the mel powers (include/mts.h mts_mfcc_frames): mel fp32 [total_frames, n_mels], frame_start int64
+    [n_sent + 1], dct fp32 [n_mfcc, n_mels].  out: fp32 / bf16 [total_frames, 2 n_mfcc], unit column stride, any row stride (a column block
+    of a wider matrix: the rest of it is not touched); columns [0, n_mfcc) the MFCC, the rest the delta.  Every element of out is
+    written."""
+    assert mel.dim() == 2 and mel.dtype == torch.float32 and mel.is_contiguous() and mel.is_cuda
+    assert frame_start.dtype == torch.int64 and frame_start.dim() == 1 and frame_start.is_contiguous() and frame_start.numel() >= 2
+    assert dct.dim() == 2 and dct.dtype == torch.float32 and dct.is_contiguous() and int(dct.shape[1]) == int(mel.shape[1])
+    total_frames, n_mels = int(mel.shape[0]), int(mel.shape[1])
+    n_sent, n_mfcc = frame_start.numel() - 1, int(dct.shape[0])
+    assert out.dim() == 2 and tuple(out.shape) == (total_frames, 2 * n_mfcc) and out.stride(1) == 1
+    ld_out = int(out.stride(0)) if total_frames > 1 else max(int(out.stride(0)), 2 * n_mfcc)
+    assert mel.device == frame_start.device == dct.device == out.device
+    nbytes = int(lib.mts_mfcc_frames_workspace(n_sent, total_frames, n_mfcc))
+    work = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=mel.device)
+    check(lib.mts_mfcc_frames(stream_ptr(), dtype_code(out.dtype), n_sent, n_mels, n_mfcc, ptr(mel), total_frames, ptr(frame_start), ptr(dct),
+                              ptr(work), nbytes, ptr(out), ld_out))
+    return out
+
+
 def embed_layernorm_fwd(x, pos, pos_offset, type0, gamma, beta, eps, y, pre, mean, rstd, row_src=None, x2=None):
     """row_src (int32 [n_rows], optional): packed batch -- output row r is sentence row_src[r] = b*L + i of x.
     x2 (fp32 [B, L, D2], optional): K-split input -- the row is x[b, i] | x2[b, i] and the concatenation is never materialised."""
