@@ -1,8 +1,8 @@
 """Full self-attention (csrc/full_attn.hip) and Transformer_segmenter(restricted=False) on a real MI355X, against the fp64 oracle
 of tests/full_attention_oracle.py and the reference's fixture tests/golden/g17_full_attention.npz.
 
-Kernel level, bf16 and fp32, head dims 16 / 32 / 64 / 224 / 256, L from 1 to 2437 plus one 4096-row document, equal / ragged /
-packed lengths, attention dropout 0.1 (keep mask rebuilt on the host from include/mts.h's rule), each checked on the operands the
+Kernel level, bf16 and fp32, head dims 16 / 32 / 64 / 96 / 128 / 160 / 192 / 224 / 256 / 264 / 300 / 512 (every instantiation the
+dispatcher can select, and both refusals), L from 1 to 2437 plus one 4096-row document, equal / ragged / packed lengths, attention dropout 0.1 (keep mask rebuilt on the host from include/mts.h's rule), each checked on the operands the
 kernel got, widened to fp64:
   * ctx, lse, dq / dk / dv: the elementwise bars and L2 ratio of test_gpu_band_hd224.py; padded query rows equal to the oracle (not
     zero); dk / dv of padded keys exactly 0;
@@ -38,6 +38,16 @@ CASES = {
     'L1':             (1, 1, 448, 2, None, False, 0.0),
     'L2437':          (1, 2437, 448, 2, None, False, 0.0),
     'L4096':          (1, 4096, 64, 2, [4096], True, 0.0),
+    # the instantiations no case above selects (tests/test_instantiation_cover_cpu.py keeps the list): KK = 3 .. 6 of the matrix-core
+    # kernels at 64 + 6 query rows (two query tiles), 2 x 32 + 6 keys (a ragged last key step) and a short document; MAXU = 16 of the
+    # generic kernels (head dims above 256); both sides of the two refusals.  An 8th field names the modes that must refuse the case.
+    'hd96':            (2, 70, 192, 2, [70, 33], False, 0.0),
+    'hd128_packed':    (2, 70, 256, 2, [70, 33], True, 0.1),
+    'hd160_drop':      (2, 70, 320, 2, [70, 33], False, 0.1),
+    'hd192':           (2, 70, 384, 2, [70, 1], False, 0.0),
+    'hd264':           (2, 70, 528, 2, [70, 33], False, 0.0),                        # 264 % 32 != 0: bf16 'mfma' runs the generic kernels
+    'hd300_fp32_edge': (2, 70, 600, 2, [70, 33], False, 0.1, ('mfma', 'generic')),   # fp32: 162304 B of LDS; bf16: 300 % 8 != 0
+    'hd512':           (2, 40, 1024, 2, [40, 9], False, 0.0, ('fp32',)),             # bf16: 141824 B of LDS; fp32: 272896 B
 }
 MODES = ('mfma', 'generic', 'fp32')     # mfma: bf16, matrix-core kernels where hd % 32 == 0; generic: bf16 with full_mfma 0
 
@@ -46,8 +56,16 @@ def _seed(name):
     return 104729 * (1 + list(CASES).index(name))
 
 
+def _case(name):
+    return CASES[name][:7]
+
+
+def _refused_in(name):
+    return CASES[name][7] if len(CASES[name]) > 7 else ()
+
+
 def _inputs(name, dtype):
-    B, Lq, D, heads, lengths, packed, p = CASES[name]
+    B, Lq, D, heads, lengths, packed, p = _case(name)
     g = torch.Generator().manual_seed(2000 + list(CASES).index(name))
     qkv = torch.randn(B, Lq, 3, D, generator=g) * 0.7
     qkv[:, :, 0] /= math.sqrt(D // heads) / 2.0               # q as the model feeds it (pre-scaled), a little sharper than uniform
@@ -79,7 +97,7 @@ def _guarded(rows, cols, dtype):
 @pytest.mark.parametrize('name,mode', [(c, m) for c in CASES for m in MODES])
 def test_full_attention_against_the_oracle(name, mode):
     from multimodaltopicsegmentation_amd import _lib as L, ops
-    B, Lq, D, heads, lengths, packed, p = CASES[name]
+    B, Lq, D, heads, lengths, packed, p = _case(name)
     hd = D // heads
     dtype = torch.float32 if mode == 'fp32' else torch.bfloat16
     qkv, dctx = _inputs(name, dtype)
@@ -109,6 +127,19 @@ def test_full_attention_against_the_oracle(name, mode):
     gbuf, dqkv = _guarded(n_rows, 3 * D, dtype)
     dbias = torch.full((3 * D,), float('nan'), device=DEV)
     seed = _seed(name)
+    if mode in _refused_in(name):                          # outside the entry points' contract: refused before any launch, nothing written
+        try:
+            L.check(L.lib.mts_set_option(b'full_mfma', 0 if mode == 'generic' else 1))
+            with pytest.raises(NotImplementedError):
+                ops.full_attn_fwd(qd, li32, B, Lq, D, heads, ctx, lse, row0=row0, drop_p=p, drop_seed=seed)
+            with pytest.raises(NotImplementedError):
+                ops.full_attn_bwd(qd, li32, lse, ctx, dd, B, Lq, D, heads, dqkv, dbias=dbias, row0=row0, drop_p=p, drop_seed=seed)
+            torch.cuda.synchronize()
+        finally:
+            L.check(L.lib.mts_set_option(b'full_mfma', 1))
+        for buf, what in ((cbuf, 'ctx'), (lbuf, 'lse'), (gbuf, 'dqkv'), (dbias, 'dbias')):
+            assert torch.isnan(buf.float()).all(), f'{what}: written by a refused call'
+        return
     try:
         L.check(L.lib.mts_set_option(b'full_mfma', 0 if mode == 'generic' else 1))
         ops.full_attn_fwd(qd, li32, B, Lq, D, heads, ctx, lse, row0=row0, drop_p=p, drop_seed=seed)
@@ -158,6 +189,32 @@ def test_full_attention_against_the_oracle(name, mode):
     for kk, (what, ref) in enumerate((('dq', q.grad / math.sqrt(hd)), ('dk', k_.grad), ('dv', v.grad))):
         worst[what] = _check(g5[:, kk], ref.reshape(B * Lq, heads, hd)[sel], msg=what, **tolb)
     print(f'\nfull attention {name} [{mode}] worst (max-ratio, L2 ratio): ' + ', '.join(f'{k} {a:.2e} / {b:.2e}' for k, (a, b) in worst.items()))
+
+
+def test_the_lds_bound_is_where_full_fill_puts_it():
+    """full_fill refuses a shape whose generic kernels need more than 160 KiB of LDS (128 row strides + 8704 bytes).  In fp32 that puts
+    the bound between head dims 300 (162304 bytes: accepted, case hd300_fp32_edge) and 304 (166400 bytes): 304 is refused by the forward
+    and by the backward, nothing written."""
+    from multimodaltopicsegmentation_amd import ops
+    from tests.test_instantiation_cover_cpu import full_generic_lds
+    assert full_generic_lds(300, 4) == 162304 <= 160 * 1024 < full_generic_lds(304, 4) == 166400
+    assert CASES['hd300_fp32_edge'][2] // CASES['hd300_fp32_edge'][3] == 300 and 'fp32' not in _refused_in('hd300_fp32_edge')
+    B, Lq, D, heads = 1, 8, 608, 2
+    qbuf, qd = _guarded(B * Lq, 3 * D, torch.float32)
+    qd.copy_(torch.randn(B * Lq, 3 * D))
+    dbuf, dd = _guarded(B * Lq, D, torch.float32)
+    dd.copy_(torch.randn(B * Lq, D))
+    cbuf, ctx = _guarded(B * Lq, D, torch.float32)
+    lbuf, lse = _guarded(B * Lq, heads, torch.float32)
+    gbuf, dqkv = _guarded(B * Lq, 3 * D, torch.float32)
+    dbias = torch.full((3 * D,), float('nan'), device=DEV)
+    with pytest.raises(NotImplementedError, match='LDS'):
+        ops.full_attn_fwd(qd, None, B, Lq, D, heads, ctx, lse)
+    with pytest.raises(NotImplementedError, match='LDS'):
+        ops.full_attn_bwd(qd, None, lse, ctx, dd, B, Lq, D, heads, dqkv, dbias=dbias)
+    torch.cuda.synchronize()
+    for buf, what in ((cbuf, 'ctx'), (lbuf, 'lse'), (gbuf, 'dqkv'), (dbias, 'dbias')):
+        assert torch.isnan(buf).all(), f'{what}: written by a refused call'
 
 
 # ------------------------------------------------------------------------------------------------ model level

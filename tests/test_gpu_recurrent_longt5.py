@@ -161,6 +161,24 @@ def test_local_attention_refuses_misaligned_operands_before_launch():
     x = torch.zeros(4 * 64 + 1, device='cuda')[1:].view(4, 64)
     with pytest.raises(NotImplementedError):
         ops.rmsnorm_fwd(x, torch.ones(64, device='cuda'), 1e-6, torch.zeros(4, 64, device='cuda'), torch.zeros(4, 1, device='cuda'))
+    # RMSNorm: D above 8 x 256 columns, D no multiple of 4 (NotImplementedError); dx aliasing x (ValueError).  Nothing is written.
+    for dtype in (torch.float32, torch.bfloat16):
+        for D in (2052, 6):
+            x, dy = torch.ones(3, D, dtype=dtype, device='cuda'), torch.ones(3, D, dtype=dtype, device='cuda')
+            w, rstd = torch.ones(D, device='cuda'), torch.full((3, 1), 7.0, device='cuda')
+            y, dx, dw = torch.full_like(x, 7.0), torch.full_like(x, 7.0), torch.full((D,), 7.0, device='cuda')
+            with pytest.raises(NotImplementedError):
+                ops.rmsnorm_fwd(x, w, 1e-6, y, rstd)
+            with pytest.raises(NotImplementedError):
+                ops.rmsnorm_bwd(x, dy, w, rstd, dx, dw)
+            torch.cuda.synchronize()
+            assert (y == 7.0).all() and (rstd == 7.0).all() and (dx == 7.0).all() and (dw == 7.0).all()
+        x, dy = torch.ones(3, 64, dtype=dtype, device='cuda'), torch.ones(3, 64, dtype=dtype, device='cuda')
+        w, rstd, dw = torch.ones(64, device='cuda'), torch.ones(3, 1, device='cuda'), torch.full((64,), 7.0, device='cuda')
+        with pytest.raises(ValueError):
+            ops.rmsnorm_bwd(x, dy, w, rstd, x, dw)
+        torch.cuda.synchronize()
+        assert (x == 1.0).all() and (dw == 7.0).all()
 
 
 def test_local_attention_refuses_other_head_dims_before_launch():
@@ -169,8 +187,21 @@ def test_local_attention_refuses_other_head_dims_before_launch():
     assert rc == 2
 
 
+# (rows, D).  Lane l of a row's wave holds columns 4 l + 256 k, k < NV = 1 / 2 / 4 / 8 (tests/test_instantiation_cover_cpu.py keeps
+# the list of what has to be reached)
+RMS_CASES = [(1, 64), (37, 128), (16384, 512), (300, 1792),
+             (2, 4),                 # the smallest D: one live lane
+             (5, 260),               # NV = 2, the second slot holds 4 columns; D % 16 = 4 in the dw reduce
+             (70, 772),              # NV = 4, last slot partial; 18 backward workgroups: the reduce's 16 parts are unevenly filled
+             (9, 1024),              # NV = 4 full
+             (1030, 768),            # NV = 4; 258 row groups on 256 workgroups: the backward strides; rows % 4 = 2
+             (3, 2044),              # NV = 8, last slot partial
+             (6, 2048),              # NV = 8 full, the largest D
+             (3, 256)]               # NV = 1 full
+
+
 @pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16], ids=['fp32', 'bf16'])
-@pytest.mark.parametrize('rows,D', [(1, 64), (37, 128), (16384, 512), (300, 1792)])
+@pytest.mark.parametrize('rows,D', RMS_CASES)
 def test_rmsnorm_kernels_against_fp64(rows, D, dtype):
     from multimodaltopicsegmentation_amd import ops
     torch.manual_seed(rows + D)

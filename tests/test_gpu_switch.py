@@ -19,7 +19,19 @@ DTYPES = {'fp32': torch.float32, 'bf16': torch.bfloat16}
 # (B, L, D, n_out, domains): one row; two documents that both read document 0; odd row counts, mixed groups 3 / 2 and 1 / 4; a head nobody
 # uses; D = 528 (no multiple of 256: the bounds-checked parameter kernel, 3 column slots with the last one partial); the bench shape
 KERNEL_CASES = [(1, 1, 16, 1, [1]), (2, 2, 16, 1, [1, 0]), (5, 23, 64, 2, [1, 0, 1, 1, 0]), (5, 7, 32, 1, [0, 1, 1, 1, 1]),
-                (3, 257, 512, 1, [0, 0, 0]), (4, 64, 528, 2, [1, 1, 0, 1]), (64, 256, 512, 1, [i & 1 for i in range(64)])]
+                (3, 257, 512, 1, [0, 0, 0]), (4, 64, 528, 2, [1, 1, 0, 1]), (64, 256, 512, 1, [i & 1 for i in range(64)]),
+                # the parameter pass's other instantiations (tests/test_instantiation_cover_cpu.py keeps the list)
+                (3, 5, 256, 3, [1, 0, 1]),              # NV = 1 full; n_out = 3
+                (2, 9, 772, 4, [0, 1]),                 # NV = 4 bounds-checked, the 4th slot holds 4 columns; n_out = 4
+                (2, 6, 1024, 2, [1, 1]),                # NV = 4 full; an idle head
+                (2, 5, 1028, 1, [1, 0]),                # NV = 8, one chunk, slot 4 holds 4 columns
+                (2, 5, 2048, 2, [0, 1]),                # NV = 8 full
+                (3, 7, 2052, 3, [1, 1, 0]),             # two chunks, the second 4 columns wide
+                (2, 3, 4096, 4, [1, 0]),                # two full-width chunks (bounds-checked: D != 2048)
+                # 2061 rows: rows % 4 == 1 and above the 512-workgroup cap, so the pass strides; head 1 has one document, so most of
+                # its workgroups take no row and flag 0 sits among flag 1
+                (9, 229, 16, 2, [0] * 8 + [1]),
+                (2, 5, 260, 2, [0, 1])]                 # NV = 2 bounds-checked, the second slot holds 4 columns
 
 
 def _reference(x, w, b, ds, doms, B, L, D, n_out):
@@ -122,6 +134,78 @@ def test_switch_head_refuses_uncovered_operands_before_launch():
         ops.switch_head_fwd(torch.ones(B * L, 18, dtype=torch.bfloat16, device=dev)[:, :16], w, b, [1, 0], B, L, sc)
     torch.cuda.synchronize()
     assert not sc.any() and not dw.any() and not db.any() and not dx.any()
+
+
+@pytest.mark.parametrize('dtype', ['fp32', 'bf16'])
+def test_parameter_pass_refuses_what_it_does_not_cover(dtype):
+    """D = 4100 > 4096: the parameter pass (two column chunks of 8 x 256 at the most) raises NotImplementedError and writes nothing; the
+    forward and the data pass have no such limit and are right there."""
+    from multimodaltopicsegmentation_amd import ops
+    B, L, D, n_out, doms = 2, 3, 4100, 2, [1, 0]
+    dt, N, dev = DTYPES[dtype], B * L, 'cuda'
+    torch.manual_seed(4100)
+    x = (torch.randn(N, D) * 0.5).to(dt).to(dev)
+    w, b, ds = (torch.randn(2, n_out, D) * 0.5).to(dev), torch.randn(2, n_out).to(dev), torch.randn(B, L, n_out).to(dev)
+    dw, db = torch.full((2, n_out, D), 7.0, device=dev), torch.full((2, n_out), 7.0, device=dev)
+    with pytest.raises(NotImplementedError, match='4096'):
+        ops.switch_head_bwd_params(x, ds, doms, B, L, dw, db)
+    scores = torch.full((N + GUARD, n_out), 7.0, device=dev)
+    ops.switch_head_fwd(x, w, b, doms, B, L, scores[:N])
+    dxb = torch.full((N + GUARD, D), 7.0, dtype=dt, device=dev)
+    ops.switch_head_bwd_data(ds, w, doms, B, L, dxb[:N])
+    torch.cuda.synchronize()
+    assert (dw == 7.0).all() and (db == 7.0).all()
+    assert (scores[N:] == 7.0).all() and (dxb[N:].float() == 7.0).all()
+    s_ref, _, _, dx_ref, unread, _ = _reference(x, w, b, ds, doms, B, L, D, n_out)
+    _check(scores[:N].view(B, L, n_out), s_ref, torch.float32, 'scores')
+    _check(dxb[:N].reshape(B, L, D), dx_ref, dt, 'dx')
+    assert unread == [1] and not dxb[:N].reshape(B, L, D)[1].any()
+
+
+@pytest.mark.parametrize('dtype', ['fp32', 'bf16'])
+def test_map_entries_outside_their_range_contribute_nothing(dtype):
+    """csrc/switch_head.hip: "A map entry outside its range contributes nothing: the row is written as 0 (forward, data) or skipped
+    (params), and no address is ever formed from it."  The wrappers build valid maps only, so the maps here are hand-built and go through
+    the C ABI.  x and ds carry one guard document of finite nonzero values in front of and behind the B documents, so whatever row a
+    kernel that ignored its range check formed from -1 or 4 lies inside the test's own buffers and shows as a wrong number."""
+    from multimodaltopicsegmentation_amd import _lib as Lb
+    from multimodaltopicsegmentation_amd.ops import dtype_code, ptr, stream_ptr
+    B, L, D, n_out = 4, 6, 64, 2
+    dt, N, dev = DTYPES[dtype], B * L, 'cuda'
+    doc_src, doc_head = [0, 4, -1, 2], [1, 0, 0, 2]
+    doc_tgt = [[-1, 4, 0, -7], [1, -1, 9, -1]]          # -7 and 9: the data pass alone reads doc_tgt, as (unsigned)tg < (unsigned)B
+    src, head = (torch.tensor(v, dtype=torch.int32, device=dev) for v in (doc_src, doc_head))
+    tgt = torch.tensor(doc_tgt, dtype=torch.int32, device=dev).reshape(-1)
+    torch.manual_seed(46)
+    xg = (torch.randn((B + 2) * L, D) * 0.5 + 3.0).to(dt).to(dev)          # guard documents included: nowhere near 0
+    dsg = (torch.randn(B + 2, L, n_out) + 3.0).to(dev)
+    w, b = (torch.randn(2, n_out, D) * 0.5).to(dev), (torch.randn(2, n_out) + 3.0).to(dev)
+    x, ds = xg[L:L + N], dsg[1:1 + B]                                      # the interior: what the kernels are handed
+    scores = torch.full((N + GUARD, n_out), 7.0, device=dev)
+    dw, db = torch.full((2, n_out, D), 7.0, device=dev), torch.full((2, n_out), 7.0, device=dev)
+    dxb = torch.full((N + GUARD, D), 7.0, dtype=dt, device=dev)
+    ws = torch.empty(Lb.lib.mts_switch_head_bwd_workspace(D), dtype=torch.uint8, device=dev)
+    code = dtype_code(dt)
+    Lb.check(Lb.lib.mts_switch_head_fwd(stream_ptr(), code, B, L, D, n_out, ptr(x), D, ptr(w), ptr(b), ptr(src), ptr(head), ptr(scores)))
+    Lb.check(Lb.lib.mts_switch_head_bwd_params(stream_ptr(), code, B, L, D, n_out, ptr(x), D, ptr(ds), ptr(src), ptr(head), ptr(dw), ptr(db),
+                                               ptr(ws)))
+    Lb.check(Lb.lib.mts_switch_head_bwd_data(stream_ptr(), code, B, L, D, n_out, ptr(ds), ptr(w), ptr(tgt), ptr(dxb), D))
+    torch.cuda.synchronize()
+    x64, d64, w64, b64 = x.double().cpu().view(B, L, D), ds.double().cpu(), w.double().cpu(), b.double().cpu()
+    sc = scores[:N].view(B, L, n_out)
+    assert (scores[N:] == 7.0).all() and (dxb[N:].float() == 7.0).all()
+    # forward: document 0 from its own rows under head 1; source 4, source -1 and head 2 are out of range: exact zeros, no bias either
+    _check(sc[0], x64[0] @ w64[1].t() + b64[1], torch.float32, 'scores of document 0')
+    assert not sc[1:].any()
+    # parameters: document 0's contribution only, under head 1; head 0 (documents 1 and 2, neither with a source in range): exact zeros
+    _check(dw[1], d64[0].t() @ x64[0], torch.float32, 'dw of head 1')
+    _check(db[1], d64[0].sum(0), torch.float32, 'db of head 1')
+    assert not dw[0].any() and not db[0].any()
+    # data: row 0 is read by document 1 under head 1, row 2 by document 0 under head 0; rows 1 and 3 have no entry in range: exact zeros
+    dx = dxb[:N].view(B, L, D)
+    _check(dx[0], d64[1] @ w64[1], dt, 'dx of document 0')
+    _check(dx[2], d64[0] @ w64[0], dt, 'dx of document 2')
+    assert not dx[1].any() and not dx[3].any()
 
 
 # ------------------------------------------------------------------------------------------------ model level
