@@ -361,6 +361,111 @@ int mts_mfcc_frames(void* stream, int out_dtype, int n_sent, int n_mels, int n_m
                     void* workspace, size_t workspace_bytes,
                     void* out,                  /* device: row f at out + f * ld_out, 2 n_mfcc columns written */
                     int64_t ld_out);
+/* PROSODIC SENTENCE FEATURES FROM RESIDENT WAVEFORMS (audio.ResidentAudio.pitch / yin / prosodic; reference: extract_acoustic_features.py
+ * :20-55 and :74-108, the `prosodic` encoder of train_fit.py:245 (167 wide): librosa.pyin(y, fmin=70, fmax=500, sr=16000), the pause and
+ * voiced-segment statistics of its voicing probability, mean and std of librosa.feature.melspectrogram(y, n_mels=40) and of its
+ * librosa.feature.delta, and the pitch jump against the previous sentence's librosa.yin track), csrc/prosody.hip.  The definition is
+ * librosa 0.8.1's, restated; parity with librosa itself is UNPINNED (the tests' oracle is a NumPy restatement of these lines).  RECALLED
+ * rather than read, and named as such: the window-edge indexing of the difference function (j = 1 .. W below), the transition width
+ * (round(35.92 * 12 * hop / sr) semitones * 10 + 1 = 141) and the Beta(2, 18) / Boltzmann(2) / 0.01 priors.  Sentences, frames and the
+ * reflect fold are those of the MFCC block above (frame_length = 2048, hop = 512, T = 1 + n / hop at the defaults).
+ *   difference  d(tau) = sum_{j=1..W} fl(fl(x[j] - x[j + tau])^2), tau = 1 .. max_period, x the frame_length samples of the frame, W = win_length:
+ *               eight chains (chain u takes j = 1 + u, 9 + u, ..) added as ((a0 + a1) + (a2 + a3)) + ((a4 + a5) + (a6 + a7)).  The DIRECT
+ *               form -- a deviation on purpose: librosa takes the products from an FFT autocorrelation and zeroes |.| < 1e-6;
+ *   cmnd        c[i] = fl(d(tau) / fl(fl(cs(tau) / tau) + FLT_MIN)), tau = min_period + i, i = 0 .. n_lags - 1 = max_period - min_period,
+ *               cs(tau) = d(1) + .. + d(tau): lane l of 64 owns the lags l k + 1 .. (l + 1) k (k = ceil(max_period / 64)), a chain inside,
+ *               the lanes' totals scanned (Hillis-Steele), cs = fl(before + chain);
+ *   shift       0 at i = 0 and i = n_lags - 1, else a = fl(fl(fl(c[i-1] + c[i+1]) - fl(2 c[i])) / 2), b = fl(fl(c[i+1] - c[i-1]) / 2),
+ *               shift = fl(-b / fl(fl(2 a) + FLT_MIN)), and 0 unless |shift| <= 1 (a non-finite quotient is 0 here, NaN upstream);
+ *   trough      lag i is one iff c[i] < c[i-1] and c[i] <= c[i+1]; lag 0 iff c[0] < c[1]; the last lag iff c[n_lags-1] < c[n_lags-2];
+ *   pYIN prior  thresholds th[k] = (k + 1) / 100 and beta[k] = the Beta(2, 18) mass of ((k) / 100, (k + 1) / 100], k = 0 .. 99 (host tables,
+ *               fp64).  With the troughs in lag order, trough t of those with c < th[k] at position p of N gets boltz_fact[N] * boltz_exp[p] =
+ *               (1 - e^-2) / (1 - e^-2N) * e^-2p; prob[t] = sum over ascending k of fl(fl(fact * exp) * beta[k]) (one fp64 chain; c is
+ *               upcast for the compare).  The lowest trough (the first of equals) also gets fl(no_trough_prob * beta_head[m]), m = the
+ *               number of thresholds it is not below, beta_head[m] = sum(beta[:m]);
+ *   bins        period = (double)(min_period + lag) + (double)shift, bin = clip(rint(bins_per_octave * log2((sr / period) / fmin)), 0,
+ *               n_bins); of two troughs in one bin the LATER in lag order is kept (an assignment, not a sum); bin n_bins is dropped (it is
+ *               the first unvoiced state upstream and overwritten there); voiced_prob = clip(sum of the bins, 0, 1) (lane chains over bins
+ *               lane, lane + 64, .. and a butterfly, fp64) rounded to fp32; log-observations fp64 [2 n_bins]: log(obs + DBL_MIN) (log_floor
+ *               = log(DBL_MIN) where obs is 0), every unvoiced state log((1 - voiced_prob) / n_bins + DBL_MIN) with the UNROUNDED sum;
+ *   Viterbi     2 n_bins states, the voiced half first.  value_0[s] = fl(logobs_0[s] + linit[s]);  value_t[s] = fl(logobs_t[s] + max_j
+ *               cand(j, s)), the FIRST j among equals, with -- the order of the two additions -- cand(j, s) = fl(fl(value[j] + lsrc[2 v +
+ *               v'][bj]) + ltri[bs - bj + width / 2]) for |bs - bj| <= width / 2 (v, v' the halves and bj, bs the bins of j and s: j = v n_bins
+ *               + bj), and fl(value[j] + log_floor) outside the band: upstream's matrix is dense, log(T + tiny), and a jump out of the band costs
+ *               the floor, not infinity.  Host tables in fp64: ltri = log of the triangle window of `width` points, lsrc[2 v + v'][j] =
+ *               log(switch[v][v']) - log(the sum of the window's points that fall inside 0 .. n_bins - 1 around j) (transition_local,
+ *               no wrap, a normaliser per source row; switch [[.99, .01], [.01, .99]]), linit = log(p_init + tiny), all mass uniform on the
+ *               unvoiced half.  The last state is the first of the best; f0 = freqs[state] (the host's fmin 2^(bin / 120), fp32), NaN and
+ *               flag 0 in the unvoiced half.  Every step is one rounded fp64 add and an exact compare: the path is bit for bit that of a
+ *               NumPy fp64 Viterbi over the same numbers.  backptr is int16 [total_frames, 2 n_bins] of workspace;
+ *   plain YIN   the first trough with c < trough_threshold (fp32 compare), else the first global minimum; f0 = fl(sr / fl((float)(min_period
+ *               + lag) + shift));
+ *   delta       the `delta` line of the MFCC block over any fp32 [total_frames, D], T < 9 -> 0 (the reference applies it to the mel POWER);
+ *   statistics  per sentence, fp64 inside (lane chains over frames lane, lane + 64, .. and a butterfly), ONE rounding to fp32 (bf16: one more
+ *               of that fp32): columns 0 .. 5 = mean and population std of f0 over its non-NaN frames (0, 0 without one), of the pause
+ *               lengths and of the voiced intensities of get_pause_durations: a pause is a run of voiced_prob < 0.5 (fp32 compare) CLOSED
+ *               by a frame that is not; without a closed run the list is [the number of pause frames] and, when that is not 0, a 0 joins
+ *               the voiced intensities.  Column jump_col = pitch_jump: 0 where doc_first[s] != 0 or s = 0 (upstream resets the previous
+ *               track per document), else nanmean(f0[: T / 5] / nanmean(f0)) - nanmean(q[Tp - ceil(Tp / 5) :] / nanmean(q)), q the
+ *               previous sentence's frames of prev_f0 (the plain-YIN track), NaN -> 0 (a sentence without a voiced frame gives 0).
+ * All run on the caller's stream, use no atomics and no dependence between workgroups of one launch, write every output element exactly
+ * once and give the same bits for the same inputs.  MTS_ERR_INVALID before any device work: a null pointer, an unknown out_dtype, a size
+ * < 1, frame_length odd or outside 16 .. 4096, win_length no multiple of 8, periods outside 1 <= min_period, min_period + 2 <= max_period
+ * <= frame_length - win_length - 1, n_lags < 3, Boltzmann tables shorter than n_lags / 2 + 2, an even width, a log_floor >= 0, jump_col < 6
+ * or >= ld_out, a misaligned pointer.  MTS_ERR_UNSUPPORTED: more than 1024 states, tables beyond a workgroup's 64 KiB of LDS, more frames
+ * than one launch covers. */
+int mts_yin_frames(void* stream, int n_sent, int frame_length, int win_length, int hop, int min_period, int max_period,
+                   const float* wave,           /* device [total_samples] */
+                   int64_t total_samples,
+                   const int64_t* sent_start,   /* device [n_sent] */
+                   const int64_t* sent_len,     /* device [n_sent] */
+                   const int64_t* frame_start,  /* device [n_sent + 1], ascending */
+                   int64_t total_frames,
+                   float* cmnd,                 /* device [total_frames, max_period - min_period + 1] out */
+                   float* shift);               /* device, the same shape, out */
+int mts_pyin_observe(void* stream, int64_t total_frames, int n_lags, int min_period, int n_bins, double sr, double fmin,
+                     double bins_per_octave,
+                     const float* cmnd,         /* device [total_frames, n_lags] */
+                     const float* shift,        /* device [total_frames, n_lags] */
+                     const double* thresholds,  /* device [n_thresholds], ascending */
+                     const double* beta,        /* device [n_thresholds] */
+                     const double* beta_head,   /* device [n_thresholds + 1] */
+                     int n_thresholds,
+                     const double* boltz_fact,  /* device [n_boltz] */
+                     const double* boltz_exp,   /* device [n_boltz] */
+                     int n_boltz, double no_trough_prob, double log_floor,
+                     float* voiced_prob,        /* device [total_frames] out */
+                     double* logobs);           /* device [total_frames, 2 n_bins] out */
+int mts_pyin_viterbi(void* stream, int n_sent, int n_bins, int width,
+                     const double* logobs,      /* device [total_frames, 2 n_bins] */
+                     int64_t total_frames,
+                     const int64_t* frame_start,/* device [n_sent + 1], ascending */
+                     const double* ltri,        /* device [width] */
+                     const double* lsrc,        /* device [4, n_bins] */
+                     const double* linit,       /* device [2 n_bins] */
+                     double log_floor,
+                     const float* freqs,        /* device [n_bins] */
+                     int16_t* backptr,          /* device [total_frames, 2 n_bins] workspace */
+                     int32_t* state,            /* device [total_frames] out */
+                     float* f0,                 /* device [total_frames] out */
+                     uint8_t* voiced);          /* device [total_frames] out */
+int mts_yin_pick(void* stream, int64_t total_frames, int n_lags, int min_period, float sr, float trough_threshold,
+                 const float* cmnd, const float* shift, /* device [total_frames, n_lags] */
+                 float* f0);                    /* device [total_frames] out */
+int mts_frame_delta(void* stream, int n_sent, int D,
+                    const float* x,             /* device [total_frames, D] */
+                    int64_t total_frames,
+                    const int64_t* frame_start, /* device [n_sent + 1], ascending */
+                    float* out);                /* device [total_frames, D] out */
+int mts_prosodic_stats(void* stream, int out_dtype, int n_sent,
+                       const float* f0,         /* device [total_frames]: the pYIN track, NaN where unvoiced */
+                       const float* voiced_prob,/* device [total_frames] */
+                       const float* prev_f0,    /* device [total_frames]: the plain-YIN track */
+                       int64_t total_frames,
+                       const int64_t* frame_start, /* device [n_sent + 1], ascending */
+                       const uint8_t* doc_first,/* device [n_sent]: 1 on the first sentence of a document */
+                       void* out,               /* device: row s at out + s * ld_out; columns 0 .. 5 and jump_col written */
+                       int64_t ld_out, int jump_col);
 
 /* ---------------------------------------------------------------------------------------------
  * LayerNorm family (biased variance, eps inside sqrt).

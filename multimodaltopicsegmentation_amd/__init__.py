@@ -19,9 +19,9 @@ from .evaluate import bootstrap_ci, cross_validate, evaluate, paired_bootstrap  
 from .predict import Prediction, predict, segment_audio  # noqa: F401
 from .pca import PcaReducer, pca_from_moments, project_folds  # noqa: F401
 from .frames import POOL_MODES, ResidentFrames, load_frames  # noqa: F401
-from .audio import ResidentAudio, load_wav, uniform_spans  # noqa: F401
+from .audio import ResidentAudio, beta_probs, load_wav, pyin_tables, uniform_spans  # noqa: F401
 
 __all__ = ['TextSegmenter', 'Transformer_segmenter', 'BiLSTM', 'BiLSTMLateFusion', 'BiRnnCrf', 'TransformerCRF', 'RecurrentLongT5', 'SheikhBiLSTM', 'SwitchBiLSTM', 'AudioPortionDataset',
            'AudioPortionDatasetInference', 'RestrictedTransformerEncoderLayer', 'DevicePrefetcher', 'ThresholdSweep', 'DEFAULT_THRESHOLDS', 'ResidentCorpus',
            'DocumentShardSampler', 'AugmentedCorpus', 'MaskedCorpus', 'fit', 'evaluate', 'bootstrap_ci', 'paired_bootstrap', 'cross_validate', 'Prediction', 'predict', 'segment_audio', 'PcaReducer',
-           'pca_from_moments', 'project_folds', 'POOL_MODES', 'ResidentFrames', 'load_frames', 'ResidentAudio', 'load_wav', 'uniform_spans']
+           'pca_from_moments', 'project_folds', 'POOL_MODES', 'ResidentFrames', 'load_frames', 'ResidentAudio', 'load_wav', 'uniform_spans', 'pyin_tables', 'beta_probs']

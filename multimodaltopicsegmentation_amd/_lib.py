@@ -143,6 +143,13 @@ SIGNATURES = {
     'mts_mel_frames': (_i, [_vp, _i, _i, _i, _i, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     'mts_mfcc_frames_workspace': (_sz, [_i, C.c_int64, _i]),
     'mts_mfcc_frames': (_i, [_vp, _i, _i, _i, _i, _vp, C.c_int64, _vp, _vp, _vp, _sz, _vp, C.c_int64]),
+    'mts_yin_frames': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64, _vp, _vp]),
+    'mts_pyin_observe': (_i, [_vp, C.c_int64, _i, _i, _i, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, C.c_double,
+                              C.c_double, _vp, _vp]),
+    'mts_pyin_viterbi': (_i, [_vp, _i, _i, _i, _vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp]),
+    'mts_yin_pick': (_i, [_vp, C.c_int64, _i, _i, _f, _f, _vp, _vp, _vp]),
+    'mts_frame_delta': (_i, [_vp, _i, _i, _vp, C.c_int64, _vp, _vp]),
+    'mts_prosodic_stats': (_i, [_vp, _i, _i, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64, _i]),
 }
 
 _missing = []

@@ -20,7 +20,17 @@ mode='interp') along the frames.  The arithmetic is stated in include/mts.h.
 Deviations, on purpose.  Parity with librosa itself is UNPINNED: librosa cannot run where this was built, so the tests check against a NumPy
 restatement of the lines above.  A non-finite sample is refused at upload (np.nanmean would skip what it made of it).  The sums run in the
 kernels' fixed order.  A sentence shorter than 8 * hop = 4096 samples (0.256 s) is refused here where upstream raises (librosa's delta
-needs 9 frames).  The reference's prosodic encoder (``pyin`` pitch, pauses; ``prosodic: 167``) is not built.
+needs 9 frames).
+
+The reference's other model-free audio encoder, ``prosodic`` (train_fit.py:245, 167 wide; extract_acoustic_features.py:74-108), is built on
+the same resident waveforms by csrc/prosody.hip: ``audio.pitch()`` (pYIN: f0, voicing probability, voiced flag per frame), ``audio.yin()``
+(the plain-YIN track the reference keeps of the previous sentence) and ``audio.prosodic()``: [f0 mean, f0 std, pause mean, pause std,
+voiced-intensity mean, voiced-intensity std | mel mean (40), mel std (40) | delta-mel mean (40), delta-mel std (40) | pitch_jump];
+``ResidentCorpus.with_prosodic(audio, field=...)`` carries it into a corpus.  Its definition (librosa 0.8.1's ``pyin`` / ``yin``, restated
+in include/mts.h) is UNPINNED against librosa as well, and two parts of it are RECALLED rather than read: the window-edge indexing of the
+difference function and the transition width of 141 bins.  Deviations, on purpose: the difference function is the direct sum, not librosa's
+FFT autocorrelation with its ``< 1e-6`` zeroing; a parabolic shift that is not finite is 0; the previous-sentence track resets at every
+document, as the extractor's loop does (extract_embeddings.py:502).
 """
 import os
 
@@ -93,6 +103,62 @@ def mfcc_tables(sr=16000, n_fft=2048, n_mels=128, n_mfcc=50):
     _TABLES[key] = {'window': (0.5 - 0.5 * np.cos(phase)).astype(np.float32),
                     'twiddle': np.stack([np.cos(phase), -np.sin(phase)], axis=1).astype(np.float32),
                     'mel_first': first, 'mel_ptr': ptr, 'mel_w': w, 'dct': dct.astype(np.float32)}
+    return _TABLES[key]
+
+
+def beta_probs(n_thresholds=100):
+    """-> fp64 [n_thresholds]: the mass of Beta(2, 18) between consecutive points of np.linspace(0, 1, n_thresholds + 1), from the closed form
+    of its CDF, 1 - (1 - x)^19 - 19 x (1 - x)^18 = 1 - (1 - x)^18 (1 + 18 x) (pYIN's prior over the thresholds).  The polynomial is
+    evaluated at the fp64 points in exact rational arithmetic and every mass rounded ONCE: in floating point the difference of two values
+    near 1 loses a digit that the 1e-15 agreement with scipy.stats.beta needs."""
+    from fractions import Fraction
+    x = np.linspace(0.0, 1.0, int(n_thresholds) + 1)
+    survival = [(1 - Fraction(float(v))) ** 18 * (1 + 18 * Fraction(float(v))) for v in x]
+    return np.array([float(a - b) for a, b in zip(survival[:-1], survival[1:])], dtype=np.float64)
+
+
+def pyin_tables(sr=16000, fmin=70.0, fmax=500.0, frame_length=2048, win_length=1024, hop=512):
+    """-> dict of pYIN's host tables and scalars at librosa 0.8.1's defaults, built in fp64 (cached per parameter set; include/mts.h names
+    every entry): ``min_period`` / ``max_period`` / ``n_lags``; ``n_bins`` = floor(120 log2(fmax / fmin)) + 1 pitch bins of a tenth of a
+    semitone and ``freqs`` fp32 [n_bins]; ``thresholds`` / ``beta`` [100] and ``beta_head`` [101] (sums of the first m of beta);
+    ``boltz_fact`` / ``boltz_exp`` [n_lags // 2 + 2]; ``width`` = 10 round(35.92 * 12 * hop / sr) + 1 and ``ltri`` [width] the log of the
+    triangle window; ``lsrc`` [4, n_bins] = log(switch[v][v']) - log(the window's sum inside the bins around j); ``linit`` [2 n_bins];
+    ``log_floor`` = log(tiny)"""
+    key = ('pyin', int(sr), float(fmin), float(fmax), int(frame_length), int(win_length), int(hop))
+    if key in _TABLES:
+        return _TABLES[key]
+    _, sr, fmin, fmax, frame_length, win_length, hop = key
+    if not (0.0 < fmin < fmax <= sr / 2.0):
+        raise ValueError(f'pitch: 0 < fmin < fmax <= sr / 2 is expected, not fmin={fmin}, fmax={fmax}')
+    min_period = max(int(np.floor(sr / fmax)), 1)
+    max_period = min(int(np.ceil(sr / fmin)), frame_length - win_length - 1)
+    if max_period < min_period + 2:
+        raise ValueError(f'pitch: fmin={fmin}, fmax={fmax} leave fewer than three lags ({min_period} .. {max_period})')
+    n_bins = int(np.floor(120.0 * np.log2(fmax / fmin))) + 1
+    if 2 * n_bins > 1024:
+        raise ValueError(f'pitch: fmin={fmin}, fmax={fmax} give {2 * n_bins} states; 1024 is the most the Viterbi kernel holds')
+    n_lags = max_period - min_period + 1
+    tiny = np.finfo(np.float64).tiny
+    beta = beta_probs(100)
+    n_boltz = n_lags // 2 + 2
+    count = np.arange(n_boltz, dtype=np.float64)
+    fact = np.zeros(n_boltz)
+    fact[1:] = (1.0 - np.exp(-2.0)) / (1.0 - np.exp(-2.0 * count[1:]))
+    width = 10 * int(round(35.92 * 12.0 * hop / sr)) + 1
+    half = width // 2
+    tri = 1.0 - np.abs(np.arange(width, dtype=np.float64) - half) / (half + 1.0)
+    at = np.arange(n_bins)[:, None] + np.arange(width)[None, :] - half
+    norm = np.where((at >= 0) & (at < n_bins), tri[None, :], 0.0).sum(axis=1)
+    switch = np.log(np.array([0.99, 0.01, 0.01, 0.99]))
+    linit = np.full(2 * n_bins, np.log(tiny))
+    linit[n_bins:] = np.log(1.0 / n_bins + tiny)
+    _TABLES[key] = {'sr': float(sr), 'fmin': fmin, 'fmax': fmax, 'frame_length': frame_length, 'win_length': win_length, 'hop': hop,
+                    'min_period': min_period, 'max_period': max_period, 'n_lags': n_lags, 'n_bins': n_bins, 'bins_per_octave': 120.0,
+                    'no_trough_prob': 0.01, 'log_floor': float(np.log(tiny)), 'width': width,
+                    'thresholds': np.linspace(0.0, 1.0, 101)[1:].copy(), 'beta': beta,
+                    'beta_head': np.array([np.sum(beta[:m]) for m in range(101)]), 'boltz_fact': fact, 'boltz_exp': np.exp(-2.0 * count),
+                    'freqs': (fmin * 2.0 ** (np.arange(n_bins, dtype=np.float64) / 120.0)).astype(np.float32), 'ltri': np.log(tri),
+                    'lsrc': np.ascontiguousarray(switch[:, None] - np.log(norm)[None, :]), 'linit': linit}
     return _TABLES[key]
 
 
@@ -275,3 +341,105 @@ class ResidentAudio:
         """-> [total_sentences, 4 n_mfcc] on the device: ``mfcc(**kw).pool('mean_std')``, the reference's ``mfcc`` sentence vector
         [mean x, mean dx, std x, std dx] (200 wide at the defaults)"""
         return self.mfcc(**kw).pool('mean_std')
+
+    # ---- prosodic features (csrc/prosody.hip) ----------------------------------------------------------------------------------------
+    PROSODIC_WIDTH = 167
+    PITCH_WORKSPACE = 1 << 30                  # bytes of cmnd / shift / log-observations / backpointers a chunk of sentences may take
+
+    def _frame_start_host(self):
+        start = np.zeros(self.total_sentences + 1, dtype=np.int64)
+        np.cumsum(self.frame_counts, out=start[1:])
+        return start
+
+    def _pitch_tables(self, fmin, fmax):
+        """pyin_tables with its arrays on the device (cached); ValueError for parameters the tables refuse"""
+        host = pyin_tables(self.sr, fmin, fmax)
+        if self.device.type != 'cuda':
+            return host
+        key = ('pyin', float(fmin), float(fmax))
+        if key not in self._device_tables:
+            self._device_tables[key] = {k: torch.from_numpy(v).to(self.device) for k, v in host.items() if isinstance(v, np.ndarray)}
+        return {**host, **self._device_tables[key]}
+
+    def _pitch_pass(self, who, fmin, fmax, pyin, yin, trough_threshold=0.1, workspace_bytes=None):
+        """the frame-level tracks of the whole corpus, sentence chunk by sentence chunk: the per-frame temporaries (cmnd and shift, and for
+        pYIN the fp64 log-observations and the int16 backpointers: 8.4 KB per frame at the defaults) exist for one chunk at a time, sized
+        to ``workspace_bytes`` -- never for the corpus.  -> dict of device tensors [total_frames]"""
+        tabs = self._pitch_tables(fmin, fmax)
+        if not 0.0 < float(trough_threshold):
+            raise ValueError(f'{who}: trough_threshold must be positive, not {trough_threshold}')
+        if self.device.type != 'cuda':
+            raise RuntimeError(f'ResidentAudio.{who} runs on the GPU (there is no CPU fallback)')
+        from . import ops
+        start = self._frame_start_host()
+        n_lags, S = tabs['n_lags'], 2 * tabs['n_bins']
+        per_frame = 8 * n_lags + (10 * S if pyin else 0)
+        budget = max(int(workspace_bytes if workspace_bytes is not None else self.PITCH_WORKSPACE) // per_frame, 1)
+        out = {}
+        with torch.cuda.device(self.device):
+            new = lambda dtype: torch.empty(self.total_frames, dtype=dtype, device=self.device)
+            if pyin:
+                out.update(f0=new(torch.float32), voiced_prob=new(torch.float32), voiced=new(torch.uint8))
+            if yin:
+                out['yin_f0'] = new(torch.float32)
+            a = 0
+            while a < self.total_sentences:
+                b = max(int(np.searchsorted(start, start[a] + budget, side='right')) - 1, a + 1)
+                fa, fb = int(start[a]), int(start[b])
+                local = torch.from_numpy(start[a:b + 1] - start[a]).to(self.device)
+                cmnd, shift = ops.yin_frames(self.wave, self.sent_start[a:b], self.sent_len[a:b], local, fb - fa, tabs['min_period'],
+                                             tabs['max_period'], tabs['frame_length'], tabs['win_length'], tabs['hop'])
+                if pyin:
+                    _, logobs = ops.pyin_observe(cmnd, shift, tabs, voiced_prob=out['voiced_prob'][fa:fb])
+                    ops.pyin_viterbi(logobs, local, tabs, f0=out['f0'][fa:fb], voiced=out['voiced'][fa:fb])
+                    del logobs
+                if yin:
+                    ops.yin_pick(cmnd, shift, tabs['min_period'], self.sr, trough_threshold, f0=out['yin_f0'][fa:fb])
+                del cmnd, shift
+                a = b
+        return out
+
+    def pitch(self, fmin=70.0, fmax=500.0, workspace_bytes=None):
+        """-> (f0, voiced_prob, voiced) on the device, [total_frames] each (frames of 2048 every 512 samples, sentence s owns the frames
+        ``frame_counts[:s].sum()`` onwards): pYIN as librosa 0.8.1 defines it -- ``f0`` fp32, NaN where unvoiced; ``voiced_prob`` fp32;
+        ``voiced`` bool.  ValueError for fmin / fmax the tables refuse; RuntimeError on a CPU device."""
+        r = self._pitch_pass('pitch', fmin, fmax, True, False, workspace_bytes=workspace_bytes)
+        return r['f0'], r['voiced_prob'], r['voiced'].view(torch.bool)
+
+    def yin(self, fmin=70.0, fmax=500.0, trough_threshold=0.1):
+        """-> the plain-YIN f0 per frame, fp32 [total_frames] on the device (``librosa.yin(y, fmin, fmax)``: the first trough of the
+        normalised difference function below ``trough_threshold``, else its global minimum)"""
+        return self._pitch_pass('yin', fmin, fmax, False, True, trough_threshold=trough_threshold)['yin_f0']
+
+    def prosodic(self, out_dtype=torch.float32, out=None, workspace_bytes=None):
+        """-> [total_sentences, 167] on the device in ``out_dtype`` (torch.float32 | torch.bfloat16: ONE rounding of the fp32 row), the
+        reference's ``prosodic`` sentence vector in its column order: [f0 mean, f0 std, pause mean, pause std, voiced-intensity mean,
+        voiced-intensity std, mel mean (40), mel std (40), delta-mel mean (40), delta-mel std (40), pitch_jump].  ``out``: a [total_sentences,
+        167] fp32 / bf16 view with unit column stride (a column block of a wider matrix: nothing outside it is written) to fill instead.
+        pitch_jump is 0 on the first sentence of every document.  RuntimeError on a CPU device."""
+        if out is None and out_dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f'prosodic: out_dtype is torch.float32 or torch.bfloat16, not {out_dtype}')
+        if out is not None and (out.dim() != 2 or tuple(out.shape) != (self.total_sentences, self.PROSODIC_WIDTH) or out.stride(1) != 1
+                                or out.dtype not in (torch.float32, torch.bfloat16)):
+            raise ValueError(f'prosodic: out must be a fp32 / bf16 [{self.total_sentences}, {self.PROSODIC_WIDTH}] view with unit column stride')
+        if self.device.type != 'cuda':
+            raise RuntimeError('ResidentAudio.prosodic runs on the GPU (there is no CPU fallback)')
+        from . import ops
+        tracks = self._pitch_pass('prosodic', 70.0, 500.0, True, True, workspace_bytes=workspace_bytes)
+        first = np.zeros(self.total_sentences, dtype=np.uint8)
+        first[np.concatenate([[0], np.cumsum(self.sentences)[:-1]])] = 1
+        with torch.cuda.device(self.device):
+            if out is None:
+                out = torch.empty((self.total_sentences, self.PROSODIC_WIDTH), dtype=out_dtype, device=self.device)
+            tabs = self._tables(1, 40, 2048)
+            frame_start = torch.from_numpy(self._frame_start_host()).to(self.device)
+            mel = ops.mel_frames(self.wave, self.sent_start, self.sent_len, frame_start, self.total_frames, tabs['window'], tabs['twiddle'],
+                                 tabs['mel_first'], tabs['mel_ptr'], tabs['mel_w'], self.DEFAULT_HOP)
+            ops.frame_pool(mel, frame_start, out[:, 6:86], first='mean', with_std=True)
+            delta = ops.frame_delta(mel, frame_start)
+            del mel
+            ops.frame_pool(delta, frame_start, out[:, 86:166], first='mean', with_std=True)
+            del delta
+            ops.prosodic_stats(tracks['f0'], tracks['voiced_prob'], tracks['yin_f0'], frame_start, torch.from_numpy(first).to(self.device),
+                               out, self.PROSODIC_WIDTH - 1)
+        return out

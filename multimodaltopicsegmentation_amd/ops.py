@@ -394,6 +394,107 @@ def mfcc_frames(mel, frame_start, dct, out):
     return out
 
 
+def _dev_tensor(t, dtype, numel, like):
+    assert t.dtype == dtype and t.is_contiguous() and t.numel() == numel and t.device == like.device, (t.dtype, tuple(t.shape), numel)
+    return t
+
+
+def yin_frames(wave, sent_start, sent_len, frame_start, total_frames, min_period, max_period, frame_length=2048, win_length=1024, hop=512):
+    """the cumulative-mean-normalised difference function of every frame of a resident waveform and its parabolic shifts (include/mts.h
+    mts_yin_frames); the sentence table as in mel_frames.  -> (cmnd, shift), both fp32 [total_frames, max_period - min_period + 1]."""
+    n_sent, total_frames, n_lags = sent_start.numel(), int(total_frames), int(max_period) - int(min_period) + 1
+    assert wave.dim() == 1 and wave.dtype == torch.float32 and wave.is_contiguous() and wave.is_cuda
+    _dev_tensor(sent_start, torch.int64, n_sent, wave), _dev_tensor(sent_len, torch.int64, n_sent, wave)
+    _dev_tensor(frame_start, torch.int64, n_sent + 1, wave)
+    cmnd = torch.empty((max(total_frames, 0), max(n_lags, 0)), dtype=torch.float32, device=wave.device)
+    shift = torch.empty_like(cmnd)
+    check(lib.mts_yin_frames(stream_ptr(), n_sent, int(frame_length), int(win_length), int(hop), int(min_period), int(max_period), ptr(wave),
+                             wave.numel(), ptr(sent_start), ptr(sent_len), ptr(frame_start), total_frames, ptr(cmnd), ptr(shift)))
+    return cmnd, shift
+
+
+def pyin_observe(cmnd, shift, tabs, voiced_prob=None, logobs=None):
+    """pYIN's observation model per frame (include/mts.h mts_pyin_observe): cmnd / shift fp32 [F, n_lags]; ``tabs`` the device tables of
+    ``audio.pyin_tables`` (with its scalars).  -> (voiced_prob fp32 [F], logobs fp64 [F, 2 n_bins]), every element written."""
+    assert cmnd.dim() == 2 and cmnd.dtype == torch.float32 and cmnd.is_contiguous() and cmnd.is_cuda
+    F, n_lags = int(cmnd.shape[0]), int(cmnd.shape[1])
+    _dev_tensor(shift, torch.float32, F * n_lags, cmnd)
+    n_bins, n_thr, n_boltz = int(tabs['n_bins']), tabs['thresholds'].numel(), tabs['boltz_fact'].numel()
+    _dev_tensor(tabs['thresholds'], torch.float64, n_thr, cmnd), _dev_tensor(tabs['beta'], torch.float64, n_thr, cmnd)
+    _dev_tensor(tabs['beta_head'], torch.float64, n_thr + 1, cmnd), _dev_tensor(tabs['boltz_exp'], torch.float64, n_boltz, cmnd)
+    assert tabs['boltz_fact'].dtype == torch.float64 and tabs['boltz_fact'].device == cmnd.device
+    if voiced_prob is None:
+        voiced_prob = torch.empty(F, dtype=torch.float32, device=cmnd.device)
+    if logobs is None:
+        logobs = torch.empty((F, 2 * n_bins), dtype=torch.float64, device=cmnd.device)
+    _dev_tensor(voiced_prob, torch.float32, F, cmnd), _dev_tensor(logobs, torch.float64, F * 2 * n_bins, cmnd)
+    check(lib.mts_pyin_observe(stream_ptr(), F, n_lags, int(tabs['min_period']), n_bins, float(tabs['sr']), float(tabs['fmin']),
+                               float(tabs['bins_per_octave']), ptr(cmnd), ptr(shift), ptr(tabs['thresholds']), ptr(tabs['beta']),
+                               ptr(tabs['beta_head']), n_thr, ptr(tabs['boltz_fact']), ptr(tabs['boltz_exp']), n_boltz,
+                               float(tabs['no_trough_prob']), float(tabs['log_floor']), ptr(voiced_prob), ptr(logobs)))
+    return voiced_prob, logobs
+
+
+def pyin_viterbi(logobs, frame_start, tabs, f0=None, voiced=None, state=None):
+    """the fp64 Viterbi of every sentence over its frames' log-observations (include/mts.h mts_pyin_viterbi): logobs fp64 [F, 2 n_bins],
+    frame_start int64 [n_sent + 1].  -> (state int32 [F], f0 fp32 [F], NaN where unvoiced, voiced uint8 [F]).  The int16 backpointers
+    [F, 2 n_bins] are a temporary of this call."""
+    assert logobs.dim() == 2 and logobs.dtype == torch.float64 and logobs.is_contiguous() and logobs.is_cuda
+    F, S = int(logobs.shape[0]), int(logobs.shape[1])
+    n_bins, n_sent = int(tabs['n_bins']), frame_start.numel() - 1
+    assert S == 2 * n_bins
+    _dev_tensor(frame_start, torch.int64, n_sent + 1, logobs)
+    _dev_tensor(tabs['lsrc'], torch.float64, 4 * n_bins, logobs), _dev_tensor(tabs['linit'], torch.float64, S, logobs)
+    _dev_tensor(tabs['freqs'], torch.float32, n_bins, logobs)
+    assert tabs['ltri'].dtype == torch.float64 and tabs['ltri'].is_contiguous() and tabs['ltri'].device == logobs.device
+    state = torch.empty(F, dtype=torch.int32, device=logobs.device) if state is None else state
+    f0 = torch.empty(F, dtype=torch.float32, device=logobs.device) if f0 is None else f0
+    voiced = torch.empty(F, dtype=torch.uint8, device=logobs.device) if voiced is None else voiced
+    _dev_tensor(state, torch.int32, F, logobs), _dev_tensor(f0, torch.float32, F, logobs), _dev_tensor(voiced, torch.uint8, F, logobs)
+    back = torch.empty((max(F, 1), S), dtype=torch.int16, device=logobs.device)
+    check(lib.mts_pyin_viterbi(stream_ptr(), n_sent, n_bins, tabs['ltri'].numel(), ptr(logobs), F, ptr(frame_start), ptr(tabs['ltri']),
+                               ptr(tabs['lsrc']), ptr(tabs['linit']), float(tabs['log_floor']), ptr(tabs['freqs']), ptr(back), ptr(state),
+                               ptr(f0), ptr(voiced)))
+    return state, f0, voiced
+
+
+def yin_pick(cmnd, shift, min_period, sr, trough_threshold=0.1, f0=None):
+    """the plain-YIN f0 of every frame (include/mts.h mts_yin_pick): cmnd / shift fp32 [F, n_lags] -> f0 fp32 [F]"""
+    assert cmnd.dim() == 2 and cmnd.dtype == torch.float32 and cmnd.is_contiguous() and cmnd.is_cuda
+    F, n_lags = int(cmnd.shape[0]), int(cmnd.shape[1])
+    _dev_tensor(shift, torch.float32, F * n_lags, cmnd)
+    f0 = torch.empty(F, dtype=torch.float32, device=cmnd.device) if f0 is None else f0
+    _dev_tensor(f0, torch.float32, F, cmnd)
+    check(lib.mts_yin_pick(stream_ptr(), F, n_lags, int(min_period), float(sr), float(trough_threshold), ptr(cmnd), ptr(shift), ptr(f0)))
+    return f0
+
+
+def frame_delta(x, frame_start):
+    """the Savitzky-Golay slope of width 9 along the frames of every sentence (include/mts.h mts_frame_delta; the delta of mfcc_frames):
+    x fp32 [F, D], frame_start int64 [n_sent + 1] -> fp32 [F, D]; 0 for a sentence of fewer than 9 frames"""
+    assert x.dim() == 2 and x.dtype == torch.float32 and x.is_contiguous() and x.is_cuda
+    n_sent = frame_start.numel() - 1
+    _dev_tensor(frame_start, torch.int64, n_sent + 1, x)
+    out = torch.empty_like(x)
+    check(lib.mts_frame_delta(stream_ptr(), n_sent, int(x.shape[1]), ptr(x), int(x.shape[0]), ptr(frame_start), ptr(out)))
+    return out
+
+
+def prosodic_stats(f0, voiced_prob, prev_f0, frame_start, doc_first, out, jump_col):
+    """the six scalar columns and pitch_jump of the prosodic sentence vector (include/mts.h mts_prosodic_stats): f0 (the pYIN track, NaN
+    where unvoiced), voiced_prob, prev_f0 (the plain-YIN track) fp32 [F]; frame_start int64 [n_sent + 1]; doc_first uint8 [n_sent].  out:
+    fp32 / bf16 [n_sent, > jump_col], unit column stride; columns 0 .. 5 and jump_col are written, nothing else."""
+    assert f0.dim() == 1 and f0.dtype == torch.float32 and f0.is_contiguous() and f0.is_cuda
+    F, n_sent = f0.numel(), frame_start.numel() - 1
+    _dev_tensor(voiced_prob, torch.float32, F, f0), _dev_tensor(prev_f0, torch.float32, F, f0)
+    _dev_tensor(frame_start, torch.int64, n_sent + 1, f0), _dev_tensor(doc_first, torch.uint8, n_sent, f0)
+    assert out.dim() == 2 and int(out.shape[0]) == n_sent and int(out.shape[1]) > int(jump_col) and out.stride(1) == 1 and out.device == f0.device
+    ld_out = int(out.stride(0)) if n_sent > 1 else max(int(out.stride(0)), int(jump_col) + 1)
+    check(lib.mts_prosodic_stats(stream_ptr(), dtype_code(out.dtype), n_sent, ptr(f0), ptr(voiced_prob), ptr(prev_f0), F, ptr(frame_start),
+                                 ptr(doc_first), ptr(out), ld_out, int(jump_col)))
+    return out
+
+
 def embed_layernorm_fwd(x, pos, pos_offset, type0, gamma, beta, eps, y, pre, mean, rstd, row_src=None, x2=None):
     """row_src (int32 [n_rows], optional): packed batch -- output row r is sentence row_src[r] = b*L + i of x.
     x2 (fp32 [B, L, D2], optional): K-split input -- the row is x[b, i] | x2[b, i] and the concatenation is never materialised."""

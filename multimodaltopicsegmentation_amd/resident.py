@@ -577,6 +577,39 @@ class ResidentCorpus:
                 out.corpus2 = frames.pool(mode, out_dtype=self.wire)
         return out
 
+    def with_prosodic(self, audio, field='embeddings'):
+        """-> a ResidentCorpus that takes one input from ``audio.prosodic()`` (an ``audio.ResidentAudio``; the reference's 167-wide
+        ``prosodic`` sentence vector, csrc/prosody.hip) in this corpus' wire dtype; ``field`` and what is shared as in ``with_frames``
+        ('append' writes the 167 columns in place behind the stored ones).  ValueError: an unknown field, audio on another device,
+        documents or sentences per document that are not this corpus'; RuntimeError on a CPU-device corpus."""
+        import copy
+        if field not in ('embeddings', 'embeddings2', 'append'):
+            raise ValueError(f"with_prosodic: field is 'embeddings', 'embeddings2' or 'append', not {field!r}")
+        if audio.n_docs != self.n_docs:
+            raise ValueError(f'with_prosodic: the audio holds {audio.n_docs} documents, the corpus {self.n_docs}')
+        bad = np.flatnonzero(audio.sentences != self.rows)
+        if bad.size:
+            d = int(bad[0])
+            raise ValueError(f'with_prosodic: document {d} has {int(self.rows[d])} sentences in the corpus but {int(audio.sentences[d])} in the audio')
+        if audio.device != self.device:
+            raise ValueError(f'with_prosodic: the audio is on {audio.device}, the corpus on {self.device}')
+        if self.device.type != 'cuda':
+            raise RuntimeError('ResidentCorpus.with_prosodic runs on the GPU (there is no CPU fallback)')
+        out = copy.copy(self)
+        out._ring, out._turn = None, 0
+        with torch.cuda.device(self.device):
+            if field == 'append':
+                D0 = int(self.corpus.shape[1])
+                wide = torch.empty((self.total_rows, D0 + audio.PROSODIC_WIDTH), dtype=self.wire, device=self.device)
+                wide[:, :D0].copy_(self.corpus)
+                audio.prosodic(out=wide[:, D0:])
+                out.corpus = wide
+            elif field == 'embeddings':
+                out.corpus = audio.prosodic(out_dtype=self.wire)
+            else:
+                out.corpus2 = audio.prosodic(out_dtype=self.wire)
+        return out
+
 
 class AugmentedCorpus:
     """A view of a ResidentCorpus with ``2 * n_docs`` virtual documents: index v < n_docs is stored document v, bit for bit what
