@@ -1011,6 +1011,75 @@ int mts_sgd_step_clipped(void* stream, size_t n, float* param, const float* grad
  * grad_scale = 1/world in the optimizer) gives the single-process gradient of the global batch. */
 int mts_scale(void* stream, size_t n, float* x, float scale);
 
+/* ---------------------------------------------------------------------------------------------
+ * wav2vec 2.0 sentence features (csrc/wav2vec2.hip): the pieces of the reference's learned audio encoder (extract_embeddings.py:173-183,
+ * Wav2Vec2Model(...).last_hidden_state per sentence) that are not a GEMM, a LayerNorm or full attention.  The encoder is composed of
+ * these and of mts_gemm / mts_layernorm_fwd / mts_full_attn_fwd in multimodaltopicsegmentation_amd/wav2vec2.py; inference only.
+ * Sentence s is the sent_len[s] samples from sent_start[s] of `wave`, as for mts_mel_frames (clamped into the waveform before any address
+ * is formed); it gives T = (n - kernel) / stride + 1 frames of layer 0, none for n < kernel.
+ *   wave_stats   stats[s] = (mean, 1 / sqrt(var + 1e-7)) of the sentence's samples, var biased as np.var (two passes); fp64 inside: lane
+ *                chains over samples tid, tid + 256, .. and a fixed tree; ONE rounding to fp32.  Wav2Vec2FeatureExtractor(do_normalize).
+ *   conv0_stats  v[t, c] = sum_k w[c, k] * fl((x[t * stride + k] - mean) * rstd), an fmaf chain over k = 0 .. kernel - 1 from 0 (conv
+ *                layer 0, C_in = 1, no bias).  gmean / grstd [n_sent, C]: the mean of v over the sentence's T frames and 1 / sqrt(var + eps),
+ *                var = E[v^2] - mean^2 >= 0 in fp64 (sums per wave over frames q, q + 4, .. , added in wave order), rounded once.  v is
+ *                never stored.
+ *   conv0        out[block_start[s] + t, c] = gelu_erf(((v[t, c] - gmean) * grstd) * gamma[c] + beta[c]) (GroupNorm(C, C) and exact GELU)
+ *                in out_dtype, v recomputed by the same chain; the rows t >= T of the sentence's block [block_start[s], block_start[s + 1])
+ *                are written as 0.  block_start: int64 [n_sent + 1] from 0 to total_rows in multiples of 64, block s at least T rows.
+ *   regroup      x [*, H] -> out [G][rows_p, H / G]: the padded row pad_start[s] + K_p / 2 + t of group g holds x[src_row0[s] + t,
+ *                g * H / G ..], t < pad_start[s + 1] - pad_start[s] - K_p / 2; every other row of out is written as 0 (the K_p / 2 rows in
+ *                front of every sentence, which close the sentence before it as well, and the rows from pad_start[n_sent] to rows_p).
+ *                With it the grouped convolution Conv1d(H, H, K_p, padding = K_p / 2, groups = G) without its last frame is, per group,
+ *                the NT product of the overlapping rows A = out_g + m * H / G (lda = H / G, K = K_p * H / G) with the weights laid
+ *                [H / G out, K_p, H / G in]: its row pad_start[s] + t is frame t of sentence s.
+ *   pos_conv     the same convolution on the matrix cores (bf16, v_mfma_f32_16x16x32_bf16, fp32 accumulation in four K quarters added
+ *                in order), with bias, exact GELU and the residual: y[dst_start[s] + t] = x[src_row0[s] + t] + gelu_erf(conv + bias),
+ *                rounded once.  w: bf16 [G][H / G][K_p * H / G] as above; tile_start: int32 [n_sent + 1], the running sum of
+ *                ceil(T_s / 64), n_tiles its last entry; T_s = dst_start[s + 1] - dst_start[s].  Zero padding is per sentence.
+ *   rows         dst[dst_start[s] + t] = src[src_row0[s] + t] (+ res[res_row0[s] + t], added in fp32) for t < dst_start[s + 1] -
+ *                dst_start[s], rounded once to dst_dtype; src and res share src_dtype; all matrices [*, D] with row stride D.
+ * All run on the caller's stream, use no atomics, write every output element exactly once and give the same bits for the same inputs; row
+ * offsets are 64-bit.  MTS_ERR_INVALID before any device work: a null pointer (res may be NULL), an unknown dtype, a size < 1, H not
+ * divisible by G, a negative eps, total_rows no multiple of 64, a matrix off its 16-byte boundary, D no multiple of 4.
+ * MTS_ERR_UNSUPPORTED before any launch: C no multiple of 8, kernel > 32, a stride whose tile of samples exceeds 64 KiB of LDS, H / G no
+ * multiple of 8, K_p odd or above 128, more rows than one launch covers; pos_conv also H / G > 64 or K_p * H / G no multiple of 128
+ * (the GEMM form serves those).
+ * ------------------------------------------------------------------------------------------- */
+int mts_w2v_wave_stats(void* stream, int n_sent,
+                       const float* wave,           /* device [total_samples] */
+                       int64_t total_samples,
+                       const int64_t* sent_start,   /* device [n_sent] */
+                       const int64_t* sent_len,     /* device [n_sent] */
+                       float* stats);               /* device [n_sent, 2] out */
+int mts_w2v_conv0_stats(void* stream, int n_sent, int C, int kernel, int stride, const float* wave, int64_t total_samples,
+                        const int64_t* sent_start, const int64_t* sent_len,
+                        const float* wave_stats,    /* device [n_sent, 2] */
+                        const float* w,             /* device [C, kernel] */
+                        float eps,
+                        float* gmean,               /* device [n_sent, C] out */
+                        float* grstd);              /* device [n_sent, C] out */
+int mts_w2v_conv0(void* stream, int out_dtype, int n_sent, int C, int kernel, int stride, const float* wave, int64_t total_samples,
+                  const int64_t* sent_start, const int64_t* sent_len, const float* wave_stats, const float* w, const float* gmean,
+                  const float* grstd,
+                  const float* gamma,               /* device [C] */
+                  const float* beta,                /* device [C] */
+                  const int64_t* block_start,       /* device [n_sent + 1] */
+                  int64_t total_rows,
+                  void* out);                       /* device [total_rows, C] out */
+int mts_w2v_regroup(void* stream, int dtype, int n_sent, int H, int G, int Kp,
+                    const void* x,                  /* device [*, H] */
+                    const int64_t* src_row0,        /* device [n_sent] */
+                    const int64_t* pad_start,       /* device [n_sent + 1] */
+                    int64_t rows_p,
+                    void* out);                     /* device [G, rows_p, H / G] out */
+int mts_w2v_rows(void* stream, int src_dtype, int dst_dtype, int n_sent, int D, const void* src, const int64_t* src_row0, const void* res,
+                 const int64_t* res_row0,
+                 const int64_t* dst_start,          /* device [n_sent + 1] */
+                 int64_t total_rows,
+                 void* dst);                        /* device [total_rows, D] out */
+int mts_w2v_pos_conv(void* stream, int n_sent, int H, int G, int Kp, const void* x, const int64_t* src_row0, const int64_t* dst_start,
+                     const int32_t* tile_start, int n_tiles, const void* w, const float* bias, void* y);
+
 #ifdef __cplusplus
 }
 #endif

@@ -150,6 +150,12 @@ SIGNATURES = {
     'mts_yin_pick': (_i, [_vp, C.c_int64, _i, _i, _f, _f, _vp, _vp, _vp]),
     'mts_frame_delta': (_i, [_vp, _i, _i, _vp, C.c_int64, _vp, _vp]),
     'mts_prosodic_stats': (_i, [_vp, _i, _i, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64, _i]),
+    'mts_w2v_wave_stats': (_i, [_vp, _i, _vp, C.c_int64, _vp, _vp, _vp]),
+    'mts_w2v_conv0_stats': (_i, [_vp, _i, _i, _i, _i, _vp, C.c_int64, _vp, _vp, _vp, _vp, _f, _vp, _vp]),
+    'mts_w2v_conv0': (_i, [_vp, _i, _i, _i, _i, _i, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp]),
+    'mts_w2v_regroup': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, C.c_int64, _vp]),
+    'mts_w2v_rows': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp]),
+    'mts_w2v_pos_conv': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
 }
 
 _missing = []

@@ -31,6 +31,11 @@ in include/mts.h) is UNPINNED against librosa as well, and two parts of it are R
 difference function and the transition width of 141 bins.  Deviations, on purpose: the difference function is the direct sum, not librosa's
 FFT autocorrelation with its ``< 1e-6`` zeroing; a parabolic shift that is not finite is 0; the previous-sentence track resets at every
 document, as the extractor's loop does (extract_embeddings.py:502).
+
+The reference's learned audio encoder, wav2vec 2.0 (extract_embeddings.py:173-183), runs on the same resident waveforms from a
+``Wav2Vec2Weights``: ``audio.wav2vec2(weights)`` is a ``ResidentFrames`` of ``last_hidden_state`` frames, ``audio.wav2vec2_stats(weights,
+mode)`` their pooled matrix without keeping the frames (wav2vec2.py, csrc/wav2vec2.hip).  Its shortest sentence is 400 samples:
+``ResidentAudio(..., min_samples=400)`` lowers the constructor's bound, which the framed features above then apply when they are called.
 """
 import os
 
@@ -206,13 +211,20 @@ class ResidentAudio:
     CPU device only the host tables exist, as for ResidentFrames.
 
     ValueError, naming the document and the sentence: an empty document, a wave that is not 1-d, a negative start, ``start >= end`` after
-    clipping, a sentence shorter than 8 * 512 = 4096 samples.  ValueError for a non-finite sample, found on the device at upload."""
+    clipping, a sentence shorter than 8 * 512 = 4096 samples.  ValueError for a non-finite sample, found on the device at upload.
+
+    ``min_samples`` (default None: the rule above, which the framed features need) lowers that bound for an audio that feeds
+    ``wav2vec2()``, whose shortest sentence is 400 samples: the constructor then refuses only sentences below ``min_samples``, and
+    ``mfcc()`` / ``pitch()`` / ``yin()`` / ``prosodic()`` apply the 4096-sample rule when they are called."""
 
     DEFAULT_HOP = 512
 
-    def __init__(self, waves, spans, device, sr=16000, unit='seconds'):
+    def __init__(self, waves, spans, device, sr=16000, unit='seconds', min_samples=None):
         if unit not in ('seconds', 'samples'):
             raise ValueError("ResidentAudio: unit must be 'seconds' or 'samples'")
+        if min_samples is not None and int(min_samples) < 1:
+            raise ValueError(f'ResidentAudio: min_samples must be positive, not {min_samples}')
+        self.min_samples = None if min_samples is None else int(min_samples)
         self.sr = int(sr)
         self.device = torch.device(device)
         if self.device.type == 'cuda' and self.device.index is None:
@@ -236,7 +248,10 @@ class ResidentAudio:
                 if b >= e:
                     raise ValueError(f'ResidentAudio: sentence {s} of document {d} is empty: samples {b} .. {e} of {int(a.shape[0])} (start >= end '
                                      'after clipping to the document)')
-                self._refuse_short(e - b, self.DEFAULT_HOP, s, d)
+                if self.min_samples is None:
+                    self._refuse_short(e - b, self.DEFAULT_HOP, s, d)
+                elif e - b < self.min_samples:
+                    raise ValueError(f'ResidentAudio: sentence {s} of document {d} has {e - b} samples, fewer than min_samples = {self.min_samples}')
                 starts.append(offset + b)
                 lens.append(e - b)
             sentences.append(len(doc_spans))
@@ -267,6 +282,13 @@ class ResidentAudio:
         if n < (_DELTA_FRAMES - 1) * hop:
             raise ValueError(f'ResidentAudio: sentence {s} of document {d} has {n} samples, fewer than the {(_DELTA_FRAMES - 1) * hop} that give '
                              f"{_DELTA_FRAMES} frames at a hop of {hop}: librosa's delta needs {_DELTA_FRAMES} frames and the reference raises there")
+
+    def _refuse_short_sentences(self, hop):
+        """the constructor's rule for the framed features, applied late to an audio built with ``min_samples``"""
+        short = np.flatnonzero(self.sample_counts < (_DELTA_FRAMES - 1) * hop)
+        if short.size:
+            d, s = self._where(int(short[0]))
+            self._refuse_short(int(self.sample_counts[short[0]]), hop, s, d)
 
     def _where(self, s):
         """flat sentence index -> (document, sentence of the document)"""
@@ -314,11 +336,8 @@ class ResidentAudio:
         if out_dtype not in (torch.float32, torch.bfloat16):
             raise ValueError(f'mfcc: out_dtype is torch.float32 or torch.bfloat16, not {out_dtype}')
         host = mfcc_tables(self.sr, n_fft, n_mels, n_mfcc)
-        if hop != self.DEFAULT_HOP:
-            short = np.flatnonzero(self.sample_counts < (_DELTA_FRAMES - 1) * hop)
-            if short.size:
-                d, s = self._where(int(short[0]))
-                self._refuse_short(int(self.sample_counts[short[0]]), hop, s, d)
+        if hop != self.DEFAULT_HOP or self.min_samples is not None:
+            self._refuse_short_sentences(hop)
         if self.device.type != 'cuda':
             raise RuntimeError('ResidentAudio.mfcc runs on the GPU (there is no CPU fallback)')
         del host
@@ -370,6 +389,7 @@ class ResidentAudio:
             raise ValueError(f'{who}: trough_threshold must be positive, not {trough_threshold}')
         if self.device.type != 'cuda':
             raise RuntimeError(f'ResidentAudio.{who} runs on the GPU (there is no CPU fallback)')
+        self._refuse_short_sentences(self.DEFAULT_HOP)
         from . import ops
         start = self._frame_start_host()
         n_lags, S = tabs['n_lags'], 2 * tabs['n_bins']
@@ -443,3 +463,93 @@ class ResidentAudio:
             ops.prosodic_stats(tracks['f0'], tracks['voiced_prob'], tracks['yin_f0'], frame_start, torch.from_numpy(first).to(self.device),
                                out, self.PROSODIC_WIDTH - 1)
         return out
+
+    # ---- wav2vec 2.0 frames (csrc/wav2vec2.hip, wav2vec2.py) -------------------------------------------------------------------------
+    W2V_WORKSPACE = 1 << 30                    # bytes of activations a chunk of sentences may take
+    W2V_STATS_MODES = ('mean', 'max', 'mean_std', 'max_std', 'last')
+
+    def _w2v_chunks(self, who, weights, out_dtype, workspace_bytes):
+        """the checks of the two wav2vec 2.0 passes and the chunking -> (frame_start [total_sentences + 1], [(a, b)]): sentences a .. b - 1
+        go through the encoder together; a chunk's activations stay within ``workspace_bytes`` (one sentence at the least) and within the
+        32-bit row indexing of the attention kernels"""
+        from . import wav2vec2 as W
+        if not isinstance(weights, W.Wav2Vec2Weights):
+            raise ValueError(f'{who}: weights must be a Wav2Vec2Weights (Wav2Vec2Weights.from_state_dict)')
+        if out_dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f'{who}: out_dtype is torch.float32 or torch.bfloat16, not {out_dtype}')
+        frames = W.frame_counts(self.sample_counts, weights.kernels, weights.strides)
+        short = np.flatnonzero(frames < 1)
+        if short.size:
+            d, s = self._where(int(short[0]))
+            raise ValueError(f'ResidentAudio: sentence {s} of document {d} has {int(self.sample_counts[short[0]])} samples, fewer than the '
+                             f"{weights.min_samples} that give one wav2vec 2.0 frame: upstream's Conv1d raises there")
+        if self.device.type != 'cuda':
+            raise RuntimeError(f'ResidentAudio.{who} runs on the GPU (there is no CPU fallback)')
+        if weights.device != self.device:
+            raise ValueError(f'{who}: the weights live on {weights.device}, the audio on {self.device}')
+        start = np.zeros(self.total_sentences + 1, dtype=np.int64)
+        np.cumsum(frames, out=start[1:])
+        cost = W.chunk_bytes(weights, self.sample_counts)
+        budget = int(workspace_bytes if workspace_bytes is not None else self.W2V_WORKSPACE)
+        rows_cap = ((1 << 31) - 1) // (3 * weights.hidden_size)        # n_sent * longest sentence of a chunk: what mts_full_attn_fwd indexes
+        chunks, a = [], 0
+        while a < self.total_sentences:
+            b, used, longest = a, 0, 0
+            while b < self.total_sentences:
+                longest_b = max(longest, int(frames[b]))
+                if b > a and (used + int(cost[b]) > budget or (b - a + 1) * longest_b > rows_cap):
+                    break
+                used, longest, b = used + int(cost[b]), longest_b, b + 1
+            chunks.append((a, b))
+            a = b
+        return start, chunks
+
+    def _w2v_pass(self, weights, start, chunks, emit, pos='auto'):
+        from . import wav2vec2 as W
+        with torch.cuda.device(self.device):
+            for a, b in chunks:
+                plan = W.ChunkPlan(self.sample_counts[a:b], weights, self.device)
+                emit(a, b, plan, lambda out: W.forward_chunk(weights, self.wave, self.sent_start[a:b], self.sent_len[a:b], plan, out, pos=pos))
+
+    def wav2vec2(self, weights, out_dtype=torch.float32, workspace_bytes=None, out=None, pos='auto'):
+        """-> ``frames.ResidentFrames`` of width ``weights.hidden_size`` on the device: ``Wav2Vec2Model(...).last_hidden_state`` of every
+        sentence, each normalised to zero mean and unit variance and encoded as a sequence of its own (wav2vec2.py).  Sentence s owns
+        T_s rows, T <- (T - k) // stride + 1 through the conv layers of its n samples (49 for 16 000 at the base configuration).  The
+        frames are made a chunk of sentences at a time: a chunk's activations (3 200 x 512 values per second of audio for the first
+        conv layer alone) stay within ``workspace_bytes`` (default 1 GiB), only the [total_frames, H] result is kept.  ``out``: a
+        contiguous [total_frames, H] fp32 / bf16 device matrix to fill instead of a new one of ``out_dtype``.  ``pos``: the positional
+        convolution's form, 'kernel' | 'gemm' | 'auto'.  ValueError, naming the document and the sentence, for a sentence that gives no
+        frame (upstream's Conv1d raises there); RuntimeError on a CPU device."""
+        start, chunks = self._w2v_chunks('wav2vec2', weights, out.dtype if out is not None else out_dtype, workspace_bytes)
+        total, H = int(start[-1]), weights.hidden_size
+        if out is None:
+            out = torch.empty((total, H), dtype=out_dtype, device=self.device)
+        elif tuple(out.shape) != (total, H) or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f'wav2vec2: out must be a contiguous [{total}, {H}] matrix on {self.device}')
+        self._w2v_pass(weights, start, chunks, lambda a, b, plan, run: run(out[int(start[a]):int(start[b])]), pos=pos)
+        return ResidentFrames.from_device(out, torch.from_numpy(start).to(self.device), self.sentences)
+
+    def wav2vec2_stats(self, weights, mode='mean_std', out_dtype=torch.float32, workspace_bytes=None, pos='auto'):
+        """-> [total_sentences, W] on the device: ``wav2vec2(weights).pool(mode)`` without keeping the frames -- every chunk is pooled into
+        its rows of the result and freed.  Modes: 'mean', 'max', 'mean_std', 'max_std', 'last'.  'delta_gap' reads the NEXT sentence's
+        first frame, which another chunk may hold: pool the frames instead, ``wav2vec2(weights).pool('delta_gap')``."""
+        if mode == 'delta_gap':
+            raise ValueError("wav2vec2_stats: 'delta_gap' reads the next sentence's first frame, which another chunk may hold; keep the frames: "
+                             "audio.wav2vec2(weights).pool('delta_gap')")
+        if mode not in self.W2V_STATS_MODES:
+            raise ValueError(f'wav2vec2_stats: mode is one of {self.W2V_STATS_MODES}, not {mode!r}')
+        start, chunks = self._w2v_chunks('wav2vec2_stats', weights, out_dtype, workspace_bytes)
+        from . import ops
+        H = weights.hidden_size
+        width = 2 * H if mode.endswith('_std') else H
+        pooled = torch.empty((self.total_sentences, width), dtype=out_dtype, device=self.device)
+
+        def emit(a, b, plan, run):
+            frames = run(torch.empty((plan.total_frames, H), dtype=out_dtype, device=self.device))
+            if mode == 'last':
+                ops.frame_edges(frames, plan.dev['frame_start'], None, pooled[a:b], 'last')
+            else:
+                ops.frame_pool(frames, plan.dev['frame_start'], pooled[a:b], first=mode.split('_')[0], with_std=mode.endswith('_std'))
+
+        self._w2v_pass(weights, start, chunks, emit, pos=pos)
+        return pooled

@@ -495,6 +495,83 @@ def prosodic_stats(f0, voiced_prob, prev_f0, frame_start, doc_first, out, jump_c
     return out
 
 
+def w2v_wave_stats(wave, sent_start, sent_len, stats=None):
+    """(mean, 1 / sqrt(var + 1e-7)) of every sentence's samples (include/mts.h mts_w2v_wave_stats) -> fp32 [n_sent, 2]"""
+    assert wave.dim() == 1 and wave.dtype == torch.float32 and wave.is_contiguous() and wave.is_cuda
+    n_sent = sent_start.numel()
+    _dev_tensor(sent_start, torch.int64, n_sent, wave), _dev_tensor(sent_len, torch.int64, n_sent, wave)
+    stats = torch.empty((n_sent, 2), dtype=torch.float32, device=wave.device) if stats is None else stats
+    _dev_tensor(stats, torch.float32, 2 * n_sent, wave)
+    check(lib.mts_w2v_wave_stats(stream_ptr(), n_sent, ptr(wave), wave.numel(), ptr(sent_start), ptr(sent_len), ptr(stats)))
+    return stats
+
+
+def w2v_conv0_stats(wave, sent_start, sent_len, wave_stats, w, stride, eps=1e-5):
+    """the GroupNorm statistics of conv layer 0 on the normalised samples (include/mts.h mts_w2v_conv0_stats): w fp32 [C, kernel]
+    -> (gmean, grstd), both fp32 [n_sent, C]; the conv output itself is never stored"""
+    n_sent, (C, kernel) = sent_start.numel(), w.shape
+    _dev_tensor(wave_stats, torch.float32, 2 * n_sent, wave), _dev_tensor(w, torch.float32, C * kernel, wave)
+    gmean = torch.empty((n_sent, C), dtype=torch.float32, device=wave.device)
+    grstd = torch.empty_like(gmean)
+    check(lib.mts_w2v_conv0_stats(stream_ptr(), n_sent, int(C), int(kernel), int(stride), ptr(wave), wave.numel(), ptr(sent_start), ptr(sent_len),
+                                  ptr(wave_stats), ptr(w), float(eps), ptr(gmean), ptr(grstd)))
+    return gmean, grstd
+
+
+def w2v_conv0(wave, sent_start, sent_len, wave_stats, w, stride, gmean, grstd, gamma, beta, block_start, total_rows, out):
+    """conv layer 0 + GroupNorm + GELU into the sentences' row blocks (include/mts.h mts_w2v_conv0): block_start int64 [n_sent + 1] in
+    multiples of 64; out fp32 / bf16 [>= total_rows, C], contiguous; every row below total_rows is written (0 behind a sentence's frames)"""
+    n_sent, (C, kernel) = sent_start.numel(), w.shape
+    _dev_tensor(block_start, torch.int64, n_sent + 1, wave)
+    _dev_tensor(gmean, torch.float32, n_sent * C, wave), _dev_tensor(grstd, torch.float32, n_sent * C, wave)
+    _dev_tensor(gamma, torch.float32, C, wave), _dev_tensor(beta, torch.float32, C, wave)
+    assert out.dim() == 2 and out.is_contiguous() and int(out.shape[1]) == C and int(out.shape[0]) >= int(total_rows) and out.device == wave.device
+    check(lib.mts_w2v_conv0(stream_ptr(), dtype_code(out.dtype), n_sent, int(C), int(kernel), int(stride), ptr(wave), wave.numel(), ptr(sent_start),
+                            ptr(sent_len), ptr(wave_stats), ptr(w), ptr(gmean), ptr(grstd), ptr(gamma), ptr(beta), ptr(block_start), int(total_rows),
+                            ptr(out)))
+    return out
+
+
+def w2v_regroup(x, src_row0, pad_start, rows_p, G, Kp, out=None):
+    """x [*, H] -> group-major, zero-padded [G, rows_p, H / G] (include/mts.h mts_w2v_regroup); every element of out is written"""
+    assert x.dim() == 2 and x.is_contiguous() and x.is_cuda
+    n_sent, H = src_row0.numel(), int(x.shape[1])
+    _dev_tensor(src_row0, torch.int64, n_sent, x), _dev_tensor(pad_start, torch.int64, n_sent + 1, x)
+    if out is None:
+        out = torch.empty((int(G), int(rows_p), H // max(int(G), 1)), dtype=x.dtype, device=x.device)
+    assert out.is_contiguous() and out.dtype == x.dtype and out.numel() == int(rows_p) * H and out.device == x.device
+    check(lib.mts_w2v_regroup(stream_ptr(), dtype_code(x.dtype), n_sent, H, int(G), int(Kp), ptr(x), ptr(src_row0), ptr(pad_start), int(rows_p),
+                              ptr(out)))
+    return out
+
+
+def w2v_rows(src, src_row0, dst_start, dst, res=None, res_row0=None):
+    """dst[dst_start[s] + t] = src[src_row0[s] + t] (+ res[res_row0[s] + t]) (include/mts.h mts_w2v_rows): compaction, residual and cast"""
+    assert src.dim() == 2 and src.is_contiguous() and src.is_cuda and dst.dim() == 2 and dst.is_contiguous() and dst.shape[1] == src.shape[1]
+    n_sent, D = src_row0.numel(), int(src.shape[1])
+    _dev_tensor(src_row0, torch.int64, n_sent, src), _dev_tensor(dst_start, torch.int64, n_sent + 1, src)
+    if res is not None:
+        assert res.dim() == 2 and res.is_contiguous() and res.dtype == src.dtype and int(res.shape[1]) == D and res.device == src.device
+        _dev_tensor(res_row0, torch.int64, n_sent, src)
+    check(lib.mts_w2v_rows(stream_ptr(), dtype_code(src.dtype), dtype_code(dst.dtype), n_sent, D, ptr(src), ptr(src_row0), ptr(res), ptr(res_row0),
+                           ptr(dst_start), int(dst.shape[0]), ptr(dst)))
+    return dst
+
+
+def w2v_pos_conv(x, src_row0, dst_start, tile_start, n_tiles, w, bias, G, Kp, y):
+    """y[dst_start[s] + t] = x[src_row0[s] + t] + gelu(grouped conv + bias) on the matrix cores (include/mts.h mts_w2v_pos_conv): bf16 x
+    [*, H] and y [total_frames, H]; w bf16 [G, H / G, K_p * H / G]; tile_start int32 [n_sent + 1]"""
+    assert x.dim() == 2 and x.is_contiguous() and x.is_cuda and x.dtype == torch.bfloat16 == y.dtype == w.dtype
+    n_sent, H = src_row0.numel(), int(x.shape[1])
+    _dev_tensor(src_row0, torch.int64, n_sent, x), _dev_tensor(dst_start, torch.int64, n_sent + 1, x), _dev_tensor(tile_start, torch.int32, n_sent + 1, x)
+    _dev_tensor(w, torch.bfloat16, H * (H // max(int(G), 1)) * int(Kp), x), _dev_tensor(bias, torch.float32, H, x)
+    assert y.dim() == 2 and y.is_contiguous() and int(y.shape[1]) == H and y.device == x.device
+    with _timed(('w2v_pos_conv', int(n_tiles), H, int(G), int(Kp))):
+        check(lib.mts_w2v_pos_conv(stream_ptr(), n_sent, H, int(G), int(Kp), ptr(x), ptr(src_row0), ptr(dst_start), ptr(tile_start), int(n_tiles), ptr(w),
+                                   ptr(bias), ptr(y)))
+    return y
+
+
 def embed_layernorm_fwd(x, pos, pos_offset, type0, gamma, beta, eps, y, pre, mean, rstd, row_src=None, x2=None):
     """row_src (int32 [n_rows], optional): packed batch -- output row r is sentence row_src[r] = b*L + i of x.
     x2 (fp32 [B, L, D2], optional): K-split input -- the row is x[b, i] | x2[b, i] and the concatenation is never materialised."""
