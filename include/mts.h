@@ -1080,6 +1080,49 @@ int mts_w2v_rows(void* stream, int src_dtype, int dst_dtype, int n_sent, int D, 
 int mts_w2v_pos_conv(void* stream, int n_sent, int H, int G, int Kp, const void* x, const int64_t* src_row0, const int64_t* dst_start,
                      const int32_t* tile_start, int n_tiles, const void* w, const float* bias, void* y);
 
+/* ---------------------------------------------------------------------------------------------
+ * Text sentence features (csrc/text_encoder.hip): the pieces of a BERT-family sentence encoder (BertModel / RobertaModel /
+ * XLMRobertaModel behind sentence-transformers' mean pooling: the reference's --encoder / --online_encoding path,
+ * EncoderDataset.py:238-250, and the RoBERTa folders of its run scripts) that are not a GEMM, a LayerNorm or mts_full_attn_fwd.  The
+ * encoder is composed of these and of mts_gemm / mts_layernorm_fwd / mts_full_attn_fwd in multimodaltopicsegmentation_amd/text.py;
+ * inference only.
+ *   text_embed   out[i, 0:H] = LayerNorm((word[ids[i]] + position[pos[i]]) + type_row) * gamma + beta, i < n_tokens: BertEmbeddings /
+ *                RobertaEmbeddings for token type 0.  The tables word [vocab, H], position [n_pos, H] and type_row [H] are in `dtype`
+ *                (MTS_F32 | MTS_BF16), gamma / beta fp32 [H] as for mts_layernorm_fwd, out in `dtype` with row stride ldo (elements;
+ *                columns H .. ldo - 1 are not touched).  pos[i] is the row of the position table: the caller has added RoBERTa's offset
+ *                (pad_token_id + 1).  One pass: the three rows are read with 16-byte accesses and summed in fp32 in the order written,
+ *                the mean and then the biased variance about it are reduced from registers, eps is inside the root
+ *                (torch.nn.functional.layer_norm), every element is stored once.  One wave per row; no workspace.
+ *                ids and pos are NOT validated on the device: 0 <= ids[i] < vocab and 0 <= pos[i] < n_pos are the caller's to guarantee
+ *                before the launch (text.py checks the corpus' largest id and longest sentence on the host); vocab and n_pos are taken
+ *                for the argument check only.
+ *                MTS_ERR_INVALID: a null pointer, an unknown dtype, a size < 1, a negative eps, ldo < H or no multiple of 4 (fp32) / 8
+ *                (bf16), a table, gamma, beta or out off its 16-byte boundary.  MTS_ERR_UNSUPPORTED: H no multiple of 4 (fp32) / 8
+ *                (bf16) or above 2048 (fp32) / 4096 (bf16).
+ *   sent_attn    full self-attention over packed SHORT sequences, bf16: operands as for mts_full_attn_fwd -- qkv [rows, 3D] with q already
+ *                scaled, ctx [rows, D]; sentence s owns the rows row0[s] .. row0[s] + lengths[s] - 1 (both int32 [n_sent], REQUIRED),
+ *                1 <= lengths[s] <= max_len.  Query i attends to every key of its sentence.  One wave owns one (sentence, head) pair and
+ *                four pairs share a workgroup; the rows of q and k are read once, straight into v_mfma_f32_16x16x32_bf16 fragments; the
+ *                softmax is exact over the whole row on the accumulators (max, exp, sum; no online rescaling), P is rounded to bf16
+ *                unnormalised and the row's 1 / sum multiplies the fp32 product P V, rounded once to bf16.  No lse (inference only), no
+ *                dropout.  Rows outside the listed ones are neither read nor written; a lengths[s] above max_len breaks the contract and is
+ *                cut to the instantiation's cover, which max_len selects: 32 tokens for max_len <= 32, else 64.
+ *                Covers head dims that are multiples of 32 up to 128 and max_len <= 64; anything else, and fp32, is
+ *                MTS_ERR_UNSUPPORTED before any launch (mts_full_attn_fwd serves it).  MTS_ERR_INVALID: a null pointer, an unknown
+ *                dtype, a size < 1, D not divisible by heads, qkv off its 16-byte boundary.
+ * Both run on the caller's stream, use no atomics, write every output element exactly once and give the same bits for the same inputs.
+ * ------------------------------------------------------------------------------------------- */
+int mts_text_embed(void* stream, int dtype, int n_tokens, int H,
+                   const int32_t* ids,              /* device [n_tokens] */
+                   const int32_t* pos,              /* device [n_tokens] */
+                   const void* word, int vocab,     /* device [vocab, H] */
+                   const void* position, int n_pos, /* device [n_pos, H] */
+                   const void* type_row,            /* device [H] */
+                   const float* gamma, const float* beta, float eps,
+                   void* out, int ldo);             /* device [n_tokens, ldo] out */
+int mts_sent_attn_fwd(void* stream, int dtype, int n_sent, int D, int heads, const void* qkv, const int32_t* row0, const int32_t* lengths,
+                      int max_len, void* ctx);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,8 +21,10 @@ from .pca import PcaReducer, pca_from_moments, project_folds  # noqa: F401
 from .frames import POOL_MODES, ResidentFrames, load_frames  # noqa: F401
 from .audio import ResidentAudio, beta_probs, load_wav, pyin_tables, uniform_spans  # noqa: F401
 from .wav2vec2 import Wav2Vec2Weights  # noqa: F401
+from .text import ResidentText, TextEncoderWeights, tokenize_documents  # noqa: F401
 
 __all__ = ['TextSegmenter', 'Transformer_segmenter', 'BiLSTM', 'BiLSTMLateFusion', 'BiRnnCrf', 'TransformerCRF', 'RecurrentLongT5', 'SheikhBiLSTM', 'SwitchBiLSTM', 'AudioPortionDataset',
            'AudioPortionDatasetInference', 'RestrictedTransformerEncoderLayer', 'DevicePrefetcher', 'ThresholdSweep', 'DEFAULT_THRESHOLDS', 'ResidentCorpus',
            'DocumentShardSampler', 'AugmentedCorpus', 'MaskedCorpus', 'fit', 'evaluate', 'bootstrap_ci', 'paired_bootstrap', 'cross_validate', 'Prediction', 'predict', 'segment_audio', 'PcaReducer',
-           'pca_from_moments', 'project_folds', 'POOL_MODES', 'ResidentFrames', 'load_frames', 'ResidentAudio', 'load_wav', 'uniform_spans', 'pyin_tables', 'beta_probs', 'Wav2Vec2Weights']
+           'pca_from_moments', 'project_folds', 'POOL_MODES', 'ResidentFrames', 'load_frames', 'ResidentAudio', 'load_wav', 'uniform_spans', 'pyin_tables', 'beta_probs', 'Wav2Vec2Weights',
+           'ResidentText', 'TextEncoderWeights', 'tokenize_documents']

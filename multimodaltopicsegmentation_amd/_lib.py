@@ -156,6 +156,8 @@ SIGNATURES = {
     'mts_w2v_regroup': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, C.c_int64, _vp]),
     'mts_w2v_rows': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp]),
     'mts_w2v_pos_conv': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    'mts_text_embed': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _f, _vp, _i]),
+    'mts_sent_attn_fwd': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
 }
 
 _missing = []

@@ -1,6 +1,7 @@
-// Tile helpers shared by the attention translation units (band_attn.hip, full_attn.hip, t5_local_attn.hip): their kernels have
-// one lane layout, 256 threads = (row t = tid/8, group g = tid%8) over 32-row tiles staged in LDS, and the bf16 matrix-core
-// kernels of the last two have one fragment layout.  Everything is inlined; literal arguments (tile sizes, a fixed head dim) fold.
+// Tile helpers shared by the attention translation units (band_attn.hip, full_attn.hip, t5_local_attn.hip, text_encoder.hip): the
+// kernels of the first three have one lane layout, 256 threads = (row t = tid/8, group g = tid%8) over 32-row tiles staged in LDS,
+// and the bf16 matrix-core kernels of the last three have one fragment layout.  Everything is inlined; literal arguments (tile sizes,
+// a fixed head dim) fold.
 #pragma once
 #include <algorithm>
 #include "band_common.h"
@@ -127,13 +128,45 @@ __device__ __forceinline__ void attn_mm_xyt(const char* X, int xrs, int x0, cons
   }
 }
 
-// 16 x 32 coefficient tile (C layout, two 16-column halves) -> bf16 image W[16][32] of this wave (row stride TRS)
-__device__ __forceinline__ void attn_put_coef(char* W, int lane, const float (&c)[2][4]) {
+// 16 x 16 NCT coefficient tile (C layout, NCT 16-column parts) -> bf16 image W[16][16 NCT] of this wave (row stride rs bytes)
+template <int NCT>
+__device__ __forceinline__ void attn_put_coef_n(char* W, int rs, int lane, const float (&c)[NCT][4]) {
   const int l15 = lane & 15, g = lane >> 4;
 #pragma unroll
-  for (int ct = 0; ct < 2; ++ct)
+  for (int ct = 0; ct < NCT; ++ct)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) *reinterpret_cast<bf16_t*>(W + (4 * g + r) * TRS + (16 * ct + l15) * 2) = (bf16_t)c[ct][r];
+    for (int r = 0; r < 4; ++r) *reinterpret_cast<bf16_t*>(W + (4 * g + r) * rs + (16 * ct + l15) * 2) = (bf16_t)c[ct][r];
+}
+// 16 x 32 coefficient tile (two 16-column halves) -> bf16 image W[16][32] of this wave (row stride TRS)
+__device__ __forceinline__ void attn_put_coef(char* W, int lane, const float (&c)[2][4]) { attn_put_coef_n<2>(W, TRS, lane, c); }
+
+// ---- one wave per sequence (text_encoder.hip): operands straight from global memory, images private to the wave --------
+// the fragment of k-step k for row `row` of one head's slice (both operands of X . Y^T run along the head dim, so a row of q or k IS
+// the fragment: 16 bytes per lane, no staging); rows outside [0, limit) -> 0 and are never read
+__device__ __forceinline__ bf16x8 attn_gfrag(const bf16_t* __restrict__ base, int ld, int row, int limit, int k, int lane) {
+  bf16x8 f = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (row < limit) f = *reinterpret_cast<const bf16x8*>(base + (size_t)row * ld + 32 * k + 8 * (lane >> 4));
+  return f;
+}
+
+// rows [0, n) of one head's slice -> the transpose timg[d][r] (row stride rs bytes) by ONE wave; rows in [limit, n) -> 0
+__device__ __forceinline__ void attn_wave_tstage(char* timg, int rs, const bf16_t* __restrict__ base, int ld, int n, int limit, int hd, int lane) {
+  const int cpr = hd / 8;
+  for (int idx = lane; idx < n * cpr; idx += 64) {
+    const int r = idx / cpr, ch = idx % cpr;
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (r < limit) v = *reinterpret_cast<const uint4*>(base + (size_t)r * ld + ch * 8);
+    const bf16_t* e = reinterpret_cast<const bf16_t*>(&v);
+#pragma unroll
+    for (int t = 0; t < 8; ++t) *reinterpret_cast<bf16_t*>(timg + (ch * 8 + t) * rs + r * 2) = e[t];
+  }
+}
+
+// what one wave wrote to its LDS images is visible to its other lanes behind this (no workgroup barrier: the waves are independent)
+__device__ __forceinline__ void attn_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
 __device__ __forceinline__ float lanes16_max(float v) {   // over the 16 lanes that hold one row of a C fragment

@@ -572,6 +572,37 @@ def w2v_pos_conv(x, src_row0, dst_start, tile_start, n_tiles, w, bias, G, Kp, y)
     return y
 
 
+def text_embed(ids, pos, word, position, type_row, gamma, beta, eps, out):
+    """out[i, :H] = LayerNorm(word[ids[i]] + position[pos[i]] + type_row) (include/mts.h mts_text_embed): ids / pos int32 [n_tokens] on the
+    device, pos already holding the position table's row; the tables fp32 / bf16 [vocab, H], [n_pos, H], [H]; gamma / beta fp32 [H]; out
+    [n_tokens, >= H] in the tables' dtype with unit column stride (columns behind H are not touched).  The kernel trusts the ids: the
+    caller has checked them against the tables."""
+    n_tokens, (vocab, H), n_pos = ids.numel(), (int(d) for d in word.shape), int(position.shape[0])
+    _dev_tensor(ids, torch.int32, n_tokens, word), _dev_tensor(pos, torch.int32, n_tokens, word)
+    _dev_tensor(position, word.dtype, n_pos * H, word), _dev_tensor(type_row, word.dtype, H, word)
+    _dev_tensor(gamma, torch.float32, H, word), _dev_tensor(beta, torch.float32, H, word)
+    assert word.is_cuda and word.is_contiguous() and out.dim() == 2 and out.dtype == word.dtype and out.device == word.device
+    assert int(out.shape[0]) == n_tokens and int(out.shape[1]) >= H and out.stride(1) == 1
+    with _timed(('text_embed', n_tokens, H)):
+        check(lib.mts_text_embed(stream_ptr(), dtype_code(word.dtype), n_tokens, H, ptr(ids), ptr(pos), ptr(word), vocab, ptr(position), n_pos,
+                                 ptr(type_row), ptr(gamma), ptr(beta), float(eps), ptr(out), int(out.stride(0))))
+    return out
+
+
+def sent_attn_fwd(qkv, row0, lengths, max_len, D, heads, ctx):
+    """Full self-attention over packed short sequences on one wave per (sentence, head) (include/mts.h mts_sent_attn_fwd): qkv bf16
+    [rows, 3 D] with q already scaled, sentence s = rows row0[s] .. row0[s] + lengths[s] - 1 (int32 [n_sent] each, on the device), ctx bf16
+    [rows, D].  NotImplementedError where the kernel does not cover (fp32, a head dim that is no multiple of 32 or above 128, max_len
+    above 64): nothing is written then."""
+    n_sent = row0.numel()
+    assert qkv.dim() == 2 and qkv.is_cuda and qkv.is_contiguous() and int(qkv.shape[1]) == 3 * D
+    assert ctx.dim() == 2 and ctx.is_contiguous() and ctx.dtype == qkv.dtype and ctx.device == qkv.device and tuple(ctx.shape) == (int(qkv.shape[0]), D)
+    _dev_tensor(row0, torch.int32, n_sent, qkv), _dev_tensor(lengths, torch.int32, n_sent, qkv)
+    with _timed(('sent_attn_fwd', n_sent, int(max_len), D, heads)):
+        check(lib.mts_sent_attn_fwd(stream_ptr(), dtype_code(qkv.dtype), n_sent, D, heads, ptr(qkv), ptr(row0), ptr(lengths), int(max_len), ptr(ctx)))
+    return ctx
+
+
 def embed_layernorm_fwd(x, pos, pos_offset, type0, gamma, beta, eps, y, pre, mean, rstd, row_src=None, x2=None):
     """row_src (int32 [n_rows], optional): packed batch -- output row r is sentence row_src[r] = b*L + i of x.
     x2 (fp32 [B, L, D2], optional): K-split input -- the row is x[b, i] | x2[b, i] and the concatenation is never materialised."""

@@ -22,7 +22,7 @@ pass of a chunk, as the taggers compose theirs, from csrc/wav2vec2.hip and the G
 import numpy as np
 import torch
 
-_ACT = {'fp32': torch.float32, 'bf16': torch.bfloat16}
+ACT_DTYPES = {'fp32': torch.float32, 'bf16': torch.bfloat16}
 ALIGN = 64                                  # layer-0 rows a sentence's block is aligned to: 2^6 for the six stride-2 layers
 SLACK = 8                                   # rows behind a conv buffer that the overlapping reads of its last rows reach (k - 2 <= 8)
 DEFAULT_STRIDES = (5, 2, 2, 2, 2, 2, 2)
@@ -30,7 +30,7 @@ _IGNORED = ('masked_spec_embed', 'adapter.', 'quantizer.', 'project_q.', 'projec
             'feature_extractor_head.', 'tdnn.', 'objective.', 'layer_weights')
 
 
-def _cfg(config, name, default=None):
+def cfg_get(config, name, default=None):
     if config is None:
         return default
     if isinstance(config, dict):
@@ -65,7 +65,7 @@ class Wav2Vec2Weights:
 
     @classmethod
     def from_state_dict(cls, sd, config=None, device='cpu', dtype='bf16'):
-        if dtype not in _ACT:
+        if dtype not in ACT_DTYPES:
             raise ValueError("Wav2Vec2Weights: dtype must be 'bf16' or 'fp32'")
         src = {}
         for k, t in sd.items():
@@ -74,7 +74,7 @@ class Wav2Vec2Weights:
                 continue
             src[k] = t.detach().to('cpu', torch.float32).contiguous()
         self = cls.__new__(cls)
-        self.dtype, self.device = _ACT[dtype], torch.device(device)
+        self.dtype, self.device = ACT_DTYPES[dtype], torch.device(device)
         if self.device.type == 'cuda' and self.device.index is None:
             self.device = torch.device('cuda', torch.cuda.current_device())
         fe ='feature_extractor.conv_layers.'
@@ -85,18 +85,18 @@ class Wav2Vec2Weights:
             raise ValueError('Wav2Vec2Weights: the state dict holds no feature_extractor.conv_layers.*.conv.weight')
         if any(f'{fe}{i}.conv.bias' in src for i in range(n_conv)):
             raise NotImplementedError('Wav2Vec2Weights: conv_bias=True (conv biases present); only conv_bias=False is supported')
-        if any(f'{fe}{i}.layer_norm.weight' in src for i in range(1, n_conv)) or _cfg(config, 'feat_extract_norm', 'group') != 'group':
+        if any(f'{fe}{i}.layer_norm.weight' in src for i in range(1, n_conv)) or cfg_get(config, 'feat_extract_norm', 'group') != 'group':
             raise NotImplementedError("Wav2Vec2Weights: feat_extract_norm='layer' (a layer norm in every conv layer); only 'group' is supported")
         if f'{fe}0.layer_norm.weight' not in src:
             raise NotImplementedError("Wav2Vec2Weights: no group norm on conv layer 0; only feat_extract_norm='group' is supported")
-        if _cfg(config, 'do_stable_layer_norm', False):
+        if cfg_get(config, 'do_stable_layer_norm', False):
             raise NotImplementedError('Wav2Vec2Weights: do_stable_layer_norm=True; only the post-LayerNorm encoder is supported')
         for name in ('feat_extract_activation', 'hidden_act'):
-            if _cfg(config, name, 'gelu') != 'gelu':
-                raise NotImplementedError(f"Wav2Vec2Weights: {name}={_cfg(config, name)!r}; only 'gelu' is supported")
+            if cfg_get(config, name, 'gelu') != 'gelu':
+                raise NotImplementedError(f"Wav2Vec2Weights: {name}={cfg_get(config, name)!r}; only 'gelu' is supported")
         convs = [src[f'{fe}{i}.conv.weight'] for i in range(n_conv)]
         self.kernels = tuple(int(w.shape[2]) for w in convs)
-        strides = _cfg(config, 'conv_stride', DEFAULT_STRIDES)
+        strides = cfg_get(config, 'conv_stride', DEFAULT_STRIDES)
         self.strides = tuple(int(s) for s in strides)
         C = self.conv_dim = int(convs[0].shape[0])
         if len(self.strides) != n_conv:
@@ -113,17 +113,17 @@ class Wav2Vec2Weights:
         self._pos_g, self._pos_v = src[found[0][0]], src[found[0][1]]
         H, cg, Kp = (int(d) for d in self._pos_v.shape)
         self.hidden_size, self.pos_kernel = H, Kp
-        self.pos_groups = int(_cfg(config, 'num_conv_pos_embedding_groups', 16))
+        self.pos_groups = int(cfg_get(config, 'num_conv_pos_embedding_groups', 16))
         if Kp % 2:
             raise NotImplementedError(f'Wav2Vec2Weights: an odd positional kernel ({Kp}); only even kernels (which drop their last frame) are supported')
         if cg * self.pos_groups != H:
             raise ValueError(f'Wav2Vec2Weights: positional weight {tuple(self._pos_v.shape)} does not fit {self.pos_groups} groups of hidden size {H}')
-        self.eps = float(_cfg(config, 'layer_norm_eps', 1e-5))
+        self.eps = float(cfg_get(config, 'layer_norm_eps', 1e-5))
         L = 0
         while f'encoder.layers.{L}.attention.q_proj.weight' in src:
             L += 1
         self.num_layers = L
-        self.num_heads = int(_cfg(config, 'num_attention_heads', max(H // 64, 1)))
+        self.num_heads = int(cfg_get(config, 'num_attention_heads', max(H // 64, 1)))
         if H % self.num_heads:
             raise ValueError(f'Wav2Vec2Weights: hidden size {H} is not divisible by {self.num_heads} heads')
         self.intermediate_size = int(src['encoder.layers.0.feed_forward.intermediate_dense.weight'].shape[0]) if L else 0
@@ -292,30 +292,47 @@ def pos_conv_kernel_covers(w):
     return w.dtype == torch.bfloat16 and cg <= 64 and (w.pos_kernel * cg) % 128 == 0
 
 
-def transformer(w, x, plan, out=None):
-    """the encoder's LayerNorm and its post-LN layers on compact rows x [F, H] -> [F, H] (``out``: where the last LayerNorm writes)"""
+def encoder_layers(layers, cur, lengths, row0, n_seq, max_len, heads, eps, out=None, attn='full'):
+    """post-LN transformer layers on compact rows, shared by the wav2vec 2.0 encoder and the text encoder (text.py): ``cur`` [F, H] is the
+    input and the buffer the layers but the last write back to; ``lengths`` / ``row0`` (int32 [n_seq], on the device) keep every
+    sequence a sequence of its own.  ``layers``: dicts of qkv_w [3 H, H] (q | k | v), o_w, ff1_w, ff2_w in the activations' dtype and the
+    fp32 biases and LayerNorm parameters.  ``attn``: 'full' (mts_full_attn_fwd) or 'sentence' (mts_sent_attn_fwd).  -> the last
+    LayerNorm's output (``out`` if given)"""
     from . import ops
-    F, H, I, heads = plan.total_frames, w.hidden_size, w.intermediate_size, w.num_heads
-    new = lambda *shape: torch.empty(shape, dtype=w.dtype, device=x.device)
-    mean, rstd = (torch.empty(F, dtype=torch.float32, device=x.device) for _ in range(2))
-    n = len(w.layers)
-    cur = out if (n == 0 and out is not None) else new(F, H)
-    ops.layernorm_fwd(x, w.enc_gamma, w.enc_beta, w.eps, cur, mean, rstd)
+    n = len(layers)
     if n == 0:
         return cur
+    F, H = (int(d) for d in cur.shape)
+    I = int(layers[0]['ff1_w'].shape[0])
+    new = lambda *shape: torch.empty(shape, dtype=cur.dtype, device=cur.device)
+    mean, rstd = (torch.empty(F, dtype=torch.float32, device=cur.device) for _ in range(2))
     qkv, ctx, s1, a1, u, s2 = new(F, 3 * H), new(F, H), new(F, H), new(F, H), new(F, I), new(F, H)
-    lse = torch.empty((F, heads), dtype=torch.float32, device=x.device)
-    for i, p in enumerate(w.layers):
+    lse = torch.empty((F, heads), dtype=torch.float32, device=cur.device) if attn == 'full' else None
+    for i, p in enumerate(layers):
         ops.linear_fwd(cur, p['qkv_w'], p['qkv_b'], qkv, colscale=float(H // heads) ** -0.5, ncols_scaled=H)
-        ops.full_attn_fwd(qkv, plan.dev['lengths_i32'], plan.n_sent, plan.max_frames, H, heads, ctx, lse, row0=plan.dev['row0_i32'])
+        if attn == 'full':
+            ops.full_attn_fwd(qkv, lengths, n_seq, max_len, H, heads, ctx, lse, row0=row0)
+        else:
+            ops.sent_attn_fwd(qkv, row0, lengths, max_len, H, heads, ctx)
         ops.linear_fwd(ctx, p['o_w'], p['o_b'], s1, residual=cur)
-        ops.layernorm_fwd(s1, p['ln1_g'], p['ln1_b'], w.eps, a1, mean, rstd)
+        ops.layernorm_fwd(s1, p['ln1_g'], p['ln1_b'], eps, a1, mean, rstd)
         ops.linear_fwd(a1, p['ff1_w'], p['ff1_b'], u, gelu=True)
         ops.linear_fwd(u, p['ff2_w'], p['ff2_b'], s2, residual=a1)
         dst = out if (i == n - 1 and out is not None) else cur
-        ops.layernorm_fwd(s2, p['ln2_g'], p['ln2_b'], w.eps, dst, mean, rstd)
+        ops.layernorm_fwd(s2, p['ln2_g'], p['ln2_b'], eps, dst, mean, rstd)
         cur = dst
     return cur
+
+
+def transformer(w, x, plan, out=None):
+    """the encoder's LayerNorm and its post-LN layers on compact rows x [F, H] -> [F, H] (``out``: where the last LayerNorm writes)"""
+    from . import ops
+    F, H = plan.total_frames, w.hidden_size
+    mean, rstd = (torch.empty(F, dtype=torch.float32, device=x.device) for _ in range(2))
+    n = len(w.layers)
+    cur = out if (n == 0 and out is not None) else torch.empty((F, H), dtype=w.dtype, device=x.device)
+    ops.layernorm_fwd(x, w.enc_gamma, w.enc_beta, w.eps, cur, mean, rstd)
+    return encoder_layers(w.layers, cur, plan.dev['lengths_i32'], plan.dev['row0_i32'], plan.n_sent, plan.max_frames, w.num_heads, w.eps, out=out)
 
 
 def forward_chunk(w, wave, sent_start, sent_len, plan, out, pos='auto'):
